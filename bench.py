@@ -2,7 +2,7 @@
 """Headline benchmark: training samples/s of HashGrid + FullyFusedMLP(64, 2 hidden) at batch 2^18 per GPU
 (BASELINE.json `metric`; workload = BASELINE.json configs[2] / SURVEY.md 8d "cfg3").
 
-    python bench.py --gpus 1 --steps 1000 --warmup 100
+    python bench.py --gpus 1 --steps 1000 --warmup 100 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
 
@@ -10,7 +10,7 @@ One step = the reference's own benchmark step (samples/mlp_learning_an_image.cu:
 DRAW a batch of positions on the device (the library's pcg32 kernel, random.h:39-75, seed 1337 + rank), EVALUATE the regression target
 at them on the device, then trainer.training_step (grid forward -> fused MLP forward -> RelativeL2 loss -> fused MLP backward incl.
 weight gradients -> grid backward scatter -> Adam) on that batch of synthetic 3-D -> 4 samples -- all of it inside the timed region
-(`protocol` in the line says so; --no-regenerate rotates four batches that are already resident in HBM instead, and the default run
+(`protocol` in the line says so; --no-regenerate rotates four batches that are already resident in HBM instead, and a --full run
 reports that figure as well, as `value_resident`, from a second timed region of the same length).
 For N > 1 every rank trains on its own shard -- 2^18 samples each (weak scaling, the default) or 2^18 / N
 (strong scaling) -- loss gradients are normalised by the global batch, and the fp16 gradient buffer [MLP | grid]
@@ -23,15 +23,18 @@ and measurements for profiles/, not the driver's bench line):
     stress  configs[4]: HashGrid T=2^22 + FullyFusedMLP 128x4, 3-D -> 16, batch 2^18
     hash_shipped  data/config_hash.json exactly as the reference ships it, in the sample's dimensions (2-D -> 3, T = 2^15, per_level_scale 1.5,
             batch 2^18; samples/mlp_learning_an_image.cu:213): the ONE configuration the reference publishes a figure for
-            (README.md:151-153: "1000 steps ... a bit over 1 second" on an RTX 4090 ~ 240 M samples/s); the line carries the ratio as
+            (README.md:151-153: "1000 steps ... a bit over 1 second" on an RTX 4090 ~ 240 M samples/s); the --full line carries the ratio as
             `vs_reference_readme` (other hardware: not `vs_baseline`)
 `--gpus N` without a torch.distributed launcher around it re-executes itself under `python -m torch.distributed.run --nproc-per-node N`
 (free port, 127.0.0.1) and relays rank 0's line, so the plain command of the N = 1 contract works for every N.
-With N = 1 the headline line also carries `torch_binding`: the same step through the PyTorch surface most users call
+With N = 1 the --full line also carries `torch_binding`: the same step through the PyTorch surface most users call
 (tcnn.NetworkWithInputEncoding forward -> RelativeL2 in torch -> backward -> torch.optim.Adam, as samples/mlp_learning_an_image_pytorch.py
 does), timed the same way, with its ratio to the native step (README.md:208-210 quotes "much closer" than 2x at batch 2^18).
 
-Rank 0 prints ONE JSON line.  Besides the driver's contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run does only what its headline figure needs: it sets up, warms up, times --steps steps, writes
+--dump-outputs DIR if asked (dump_outputs(): what the last timed step computed, float32 .npy, <= 64 MB; same arguments, same inputs) and
+prints the contract's fields (`value`, `ms_per_step`, ...).  With --full it runs everything below as well (N > 1: `comm`, `prediction`,
+`final_loss` too), and the line carries besides
   roofline     -- the dominant kernel of the step (fixed per workload: what rocprofv3 --kernel-trace --stats shows, profiles/),
                   timed with HIP events on the stream it runs on inside the timed region (tcnn_trainer_set_profiling),
                   against the 8 TB/s HBM peak; `stages` holds the same figure for EVERY stage, from the instrumented pass;
@@ -44,7 +47,7 @@ Rank 0 prints ONE JSON line.  Besides the driver's contract fields it carries
                   line): the first ~30 steps after an idle phase run 4-8 % below the device's steady state (clocks; measured,
                   scripts/exp_first_steps.py), so the timed region of a short run would otherwise report the ramp, not the step.
 
-With --gpus 1 (no torch.distributed launcher) the measurement runs in a worker process and this process only relays its line:
+With --full --gpus 1 (no torch.distributed launcher) the measurement runs in a worker process and this process only relays its line:
 a worker that dies abnormally (a GPU memory-access fault aborts the process inside the HIP runtime, nothing can be caught
 in-process) is reported under `faulted_attempts`, the command is run ONCE more under the library's checking switches
 (TCNN_DEBUG_SYNC / TCNN_DEBUG_TRACE / TCNN_DEBUG_ALLOC=fence) to name the kernel, and the measurement is repeated, at most twice.
@@ -177,6 +180,37 @@ def make_batches(w, n, n_batches, rng, device, tcnn):
             tcnn._C.sinusoid_targets_(x, t)
         out.append((x, t))
     return out
+
+
+DUMP_BATCH_BYTES = 40 << 20  # --dump-outputs: all rows of the batch and its prediction up to this size, else a sample of rows
+
+
+def _sample(a, k):
+    """A fixed seeded sample of k rows of `a` (one per equal stratum, in order), or all of them when there are no more than k."""
+    n = a.shape[0]
+    if n <= k:
+        return a
+    stride = n // k
+    idx = np.arange(k) * stride + np.random.default_rng(1337).integers(0, stride, k)
+    return a[torch.from_numpy(idx).to(a.device)]
+
+
+def dump_outputs(out_dir, tm, x, t):
+    """--dump-outputs: the prediction of the model after the last timed step, on that step's batch (network->inference with the parameters
+    the step left behind: not the prediction the step itself computed before its update), with the batch itself, as float32 .npy files, so that two builds can be compared output for output (rows cut to a fixed
+    seeded sample where they would pass DUMP_BATCH_BYTES).  The inputs are the same bits in every run with the same arguments; training is not
+    bitwise reproducible from run to run (two runs of 1000 headline steps: predictions 2.5 % apart, norm-relative; the parameters further,
+    which is why they are not what is compared), so outputs are compared with a tolerance."""
+    rows = max(1, DUMP_BATCH_BYTES // (4 * (x.shape[1] + 2 * t.shape[1])))
+    arrays = {"inference_last_batch": _sample(tm.inference(x), rows), "last_batch_input": _sample(x, rows), "last_batch_target": _sample(t, rows)}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed 64 MB")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def cpu_model_name():
@@ -414,10 +448,17 @@ def main():
     ap.add_argument("--resident-first", action="store_true", help="diagnostic: time the resident-batch region BEFORE the regenerated one (which of two back-to-back regions is faster "
                                                                    "is a property of their order on this device, see DESIGN.md section 3)")
     ap.add_argument("--lds-budget", type=int, default=None, help="grid backward: LDS bytes per level table (tuning knob)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the per-stage breakdown and roofline, the resident-batch region, inference, the PyTorch "
+                         "binding, the CPU baseline, the accounting fields and (N = 1) the supervising worker process; without it the run sets up, warms up, "
+                         "times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the prediction of the model after the last timed step, on that step's batch, and the batch "
+                         "(float32 .npy files, 64 MB at most in all) into DIR")
     args = ap.parse_args()
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.worker:  # no launcher around this command (or a stale WORLD_SIZE=1)
         return launch_ranks(sys.argv[1:], args.gpus)
-    if args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.worker:
+    if args.full and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.worker:
         return supervise(sys.argv[1:])
     w = WORKLOADS[args.workload]
     if args.precision == "bf16":
@@ -537,15 +578,23 @@ def main():
 
     # ---- per-stage breakdown first (default): besides its numbers it brings the device to its working clocks -- measured
     # (scripts/exp_first_steps.py), the first ~30 steps after an idle phase run 4-8 % slower than the steady state, which is
-    # what a 20-step timed region straight after 5 warm-up steps would otherwise report.  The line says how many steps ran here.
-    stages, n_breakdown = breakdown_pass() if args.breakdown == "before" else (None, 0)
+    # what a 20-step timed region straight after 5 warm-up steps would otherwise report.  The line says how many steps ran here.  A plain run
+    # runs the same untimed steps without the instrumentation, so that `value` is taken at the same point as a --full run's.
+    if args.full:
+        stages, n_breakdown = breakdown_pass() if args.breakdown == "before" else (None, 0)
+    else:
+        stages, n_breakdown = None, 3 + min(args.steps, 50)
+        for i in range(n_breakdown):
+            step(i)
 
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
 
-    # ---- which stage dominates?  short untimed probe with every stage instrumented -----------------------
-    dominant = DOMINANT[args.workload] if args.dominant == "fixed" else args.dominant
+    # ---- which stage dominates?  short untimed probe with every stage instrumented (--full: the roofline's kernel) -----------------------
+    dominant = None
+    if args.full:
+        dominant = DOMINANT[args.workload] if args.dominant == "fixed" else args.dominant
     if dominant == "auto":
         tm.set_profiling(True)
         for i in range(5):
@@ -572,10 +621,11 @@ def main():
         mode["regenerate"] = True
         return out
 
-    elapsed_resident = resident_region() if regenerate and args.resident_first else None
+    elapsed_resident = resident_region() if args.full and regenerate and args.resident_first else None
 
     # ---- timed region: EXACTLY --steps steps, barrier + synchronize on both sides -----------------------
-    tm.set_profiling(True, only_stage=dominant)  # 2 HIP events per step around the dominant kernel only
+    if dominant is not None:
+        tm.set_profiling(True, only_stage=dominant)  # 2 HIP events per step around the dominant kernel only
     if dp is not None:
         dp.reset_timers()
     par.barrier()
@@ -587,6 +637,54 @@ def main():
     par.barrier()
     elapsed = time.perf_counter() - t0
     elapsed = par.all_reduce_max(elapsed, device=device)
+    if dp is not None and dp_mode == "direct" and tm.direct_status() != 0:
+        raise SystemExit(f"rank {rank}: a wait of the direct exchange timed out (phase {tm.direct_status()}): the measurement is void")
+    replicas_same = replicas_identical(tm) if dp is not None else None
+    if replicas_same is False:
+        raise SystemExit(f"rank {rank}: the replicas' parameters differ after the timed region ({dp_mode} exchange): the measurement is void")
+    # the last timed step's batch: drawn into `fresh`, or the resident batch step(steps - 1) used
+    last_batch = fresh if regenerate else batches[(args.steps - 1) % len(batches)]
+    dumped = dump_outputs(args.dump_outputs, tm, *last_batch) if args.dump_outputs and rank == 0 else None
+
+    def headline_line():
+        """The fields of the headline figure: all a plain run prints; --full adds its measurements to them."""
+        line = {
+            "metric": w["metric"] + (", 1/2/4/8 GPU" if args.workload == "hash" else ""),
+            "value": global_batch * args.steps / elapsed, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": ("bf16 (bfloat16" if args.precision == "bf16" else "f16 (fp16") + " params/activations/gradients, fp32 MFMA accumulate, fp32 Adam state)", "data": "synthetic",
+            "config": {"workload": w["describe"] + ("" if args.batch == BATCH else f" -- at a NON-DEFAULT batch of {args.batch} (exploration; the metric's batch is 2^18)"),
+                       "batch_per_gpu": local_batch, "global_batch": global_batch, "n_params": tm.n_params,
+                       "parallelism": f"dp{world} ({dp_mode})" if world > 1 else "single"},
+            "protocol": {"batches": ("regenerated inside every timed step: positions drawn with the library's pcg32 kernel, targets evaluated at them on the device, then "
+                                     "training_step (samples/mlp_learning_an_image.cu:263-271)") if regenerate else "four batches resident in HBM, rotated",
+                         "regenerate": regenerate, "timed_steps": args.steps},
+            "untimed_steps_before_timing": {"breakdown_pass" if args.full else "clock_settling": n_breakdown, "warmup": args.warmup},
+            "full": args.full,
+        }
+        if dumped is not None:
+            line["outputs_dumped"] = dumped
+        if autotune is not None:
+            line["dp_autotune"] = autotune
+        if replicas_same is not None:
+            line["replicas_identical_after_timed_region"] = replicas_same
+        return line
+
+    def finish():
+        if tcnn._C.debug_alloc_mode() != 0:
+            tcnn._C.debug_check_allocations()  # raises if any block of the checking allocator was written out of bounds
+        if dp is not None:
+            dp.close()
+        par.barrier()
+        if world > 1:
+            torch.distributed.destroy_process_group()
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_line()))
+        finish()
+        return
+
     dom_ms, dom_cnt = tm.stage_times()[dominant]
     comm = dp.comm_seconds() if dp is not None else None
     comm_phases = None
@@ -599,11 +697,6 @@ def main():
             comm_phases = {k: v / args.steps * 1e3 for k, v in dp.phase_seconds().items()}
         # the slowest rank's figure per phase is what bounds the step
         comm_phases = {k: par.all_reduce_max(v, device=device) for k, v in sorted(comm_phases.items())}
-    if dp is not None and dp_mode == "direct" and tm.direct_status() != 0:
-        raise SystemExit(f"rank {rank}: a wait of the direct exchange timed out (phase {tm.direct_status()}): the measurement is void")
-    replicas_same = replicas_identical(tm) if dp is not None else None
-    if replicas_same is False:
-        raise SystemExit(f"rank {rank}: the replicas' parameters differ after the timed region ({dp_mode} exchange): the measurement is void")
 
     if regenerate and not args.resident_first:
         elapsed_resident = resident_region()
@@ -670,14 +763,12 @@ def main():
     n_full = (tm.n_params // 32) * 32
     params_in_touched_lines = int(g_nz[:n_full].view(-1, 32).any(dim=1).sum().item()) * 32 + (tm.n_params - n_full)
     del g_nz
-    if tcnn._C.debug_alloc_mode() != 0:
-        tcnn._C.debug_check_allocations()  # raises if any block of the checking allocator was written out of bounds
 
     is_grid_workload = w["config"]["encoding"]["otype"] == "HashGrid"
     if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        value = global_batch * args.steps / elapsed
-        ab = algorithmic_bytes(w, local_batch, tm.n_params, tm.n_mlp_params)
+        line = headline_line()
+        value = line["value"]
+        ab =algorithmic_bytes(w, local_batch, tm.n_params, tm.n_mlp_params)
         if not is_grid_workload and stages and not stages.get("grid_forward"):
             # the Identity encoding ran inside the network kernel (MlpF32Input): that stage's minimum input is the caller's fp32 matrix then
             ab["mlp_train_fused"] += local_batch * (4 * w["n_in"] - 2 * (-(-w["n_in"] // 16) * 16))
@@ -714,29 +805,18 @@ def main():
             tflops = network_flops_per_sample(w) * local_batch / (net_ms * 1e-3) / 1e12
             roofline["mfma"] = {"achieved": tflops, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tflops / MFMA_PEAK_TFLOPS,
                                 "stages": "mlp_forward + mlp_backward + mlp_train_fused (the slab summation rides in the adam stage)", "ms": net_ms}
-        line = {
-            "metric": w["metric"] + (", 1/2/4/8 GPU" if args.workload == "hash" else ""),
-            "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": ("bf16 (bfloat16" if args.precision == "bf16" else "f16 (fp16") + " params/activations/gradients, fp32 MFMA accumulate, fp32 Adam state)", "data": "synthetic",
-            "config": {"workload": w["describe"] + ("" if args.batch == BATCH else f" -- at a NON-DEFAULT batch of {args.batch} (exploration; the metric's batch is 2^18)"),
-                       "batch_per_gpu": local_batch, "global_batch": global_batch, "n_params": tm.n_params,
-                       "parallelism": f"dp{world} ({dp_mode})" if world > 1 else "single"},
-            "roofline": roofline,
-            "protocol": {"batches": ("regenerated inside every timed step: positions drawn with the library's pcg32 kernel, targets evaluated at them on the device, then "
-                                     "training_step (samples/mlp_learning_an_image.cu:263-271)") if regenerate else "four batches resident in HBM, rotated",
-                         "regenerate": regenerate, "timed_steps": args.steps,
-                         "adam_touched_parameters": touched, "adam_touched_fraction": touched / tm.n_params,
-                         "adam_touched_counted_by": touched_counted_by,
-                         "nonzero_training_gradients_at_end_of_run": nonzero_training_gradients,
-                         "adam_algorithmic_bytes": {"touched": ab["adam"], "dense_upper_bound": adam_dense,
-                                                    "whole_128B_state_lines_with_a_stepped_parameter": params_in_touched_lines * 36 + (tm.n_params - params_in_touched_lines) * 2}},
+        line["roofline"] = roofline
+        line["protocol"].update({"adam_touched_parameters": touched, "adam_touched_fraction": touched / tm.n_params,
+                                 "adam_touched_counted_by": touched_counted_by,
+                                 "nonzero_training_gradients_at_end_of_run": nonzero_training_gradients,
+                                 "adam_algorithmic_bytes": {"touched": ab["adam"], "dense_upper_bound": adam_dense,
+                                                            "whole_128B_state_lines_with_a_stepped_parameter": params_in_touched_lines * 36 + (tm.n_params - params_in_touched_lines) * 2}})
+        line.update({
             "stages_ms": stages,
-            "untimed_steps_before_timing": {"breakdown_pass": n_breakdown, "warmup": args.warmup},
             "step_ideal_GBps": ab["step_ideal"] / (elapsed / args.steps) / 1e9,
             "final_loss": final_loss,
             "grid_owner_wide_slices": tcnn._C.grid_owner_wide_slices(),  # slices of the grid backward redone with 64-bit accumulators in this process (perf only)
-        }
+        })
         if elapsed_resident is not None:
             line["value_resident"] = global_batch * args.steps / elapsed_resident
             line["ms_per_step_resident"] = elapsed_resident / args.steps * 1e3
@@ -758,21 +838,13 @@ def main():
                 ms = pred["ms_per_step"]
                 line["predicted_ms_per_step"] = ms if not isinstance(ms, list) else ms
                 line["prediction"] = pred
-        if autotune is not None:
-            line["dp_autotune"] = autotune
-        if replicas_same is not None:
-            line["replicas_identical_after_timed_region"] = replicas_same
         if comm is not None:
             line["comm"] = {"seconds_per_step": comm / args.steps, "share_of_step": comm / elapsed, "phases_ms_per_step_max_over_ranks": comm_phases,
                             "note": "GPU event intervals of rank 0 around the exchange: the collectives AND, in the sharded scheme, the optimizer step on the rank's shard that sits between them"}
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(w, *batches[0], budget_s=float(os.environ.get("TCNN_BENCH_CPU_BUDGET_S", "12")), bf16=args.precision == "bf16")
         print(json.dumps(line))
-    if dp is not None:
-        dp.close()
-    par.barrier()
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -20,6 +20,8 @@ How: the reference's kernels are plain C++ between `__global__` and a handful of
   * oracle/ref_driver.cpp (ours) gives the kernels an extern "C" face: it loops (blockIdx, threadIdx) over the launch grid the
     reference's host code would use and calls the kernel body for every thread; oracle/ref_driver_mlp.cpp does the same for the
     kernels that synchronise (a block's threads are fibers, __syncthreads() switches between them).
+  * build_image_sample(): oracle/_ref/mlp_learning_an_image, a gfx950 binary with device code (not a host build), and its generated
+    source under oracle/_ref/_generated/ -- the reference's image sample, by oracle/Makefile's `image` rule; git-ignored like the rest.
 
 usage: python oracle/build_ref.py [--reference /root/reference] [--force]     (a no-op when the reference tree is absent)
 """
@@ -35,6 +37,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 OUT_DIR = os.path.join(HERE, "_ref")
 LIB = os.path.join(OUT_DIR, "libtcnn_ref.so")
 MANIFEST = os.path.join(OUT_DIR, "manifest.json")
+IMAGE = os.path.join(OUT_DIR, "mlp_learning_an_image")
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"  # a host compiler with _Float16 in C++ (g++ 11 has none)
 
 INC = "include/tiny-cuda-nn/"
@@ -125,11 +128,19 @@ def extract(path, name):
     raise RuntimeError(f"definition of {name} not found in {path}")
 
 
+def build_image_sample(reference):
+    """oracle/_ref/mlp_learning_an_image: the reference's image sample over the facade headers (oracle/Makefile `image`; it links the
+    product library, so it is built after tiny-cuda-nn_amd/lib/libtcnn_hip.so)."""
+    subprocess.check_call(["make", "-C", HERE, "-s", "image", "REFERENCE_DIR=" + os.path.abspath(reference)])
+    return os.path.exists(IMAGE)
+
+
 def build(reference="/root/reference", force=False, verbose=True):
     if not os.path.isdir(os.path.join(reference, "include", "tiny-cuda-nn")):
         if verbose:
             print(f"[build_ref] no reference tree at {reference}: keeping whatever {LIB} exists")
         return os.path.exists(LIB)
+    build_image_sample(reference)
     srcs = [os.path.join(HERE, "ref_driver.cpp"), os.path.join(HERE, "ref_driver_mlp.cpp"), os.path.join(HERE, "ref_driver_host.cpp"), os.path.join(HERE, "ref_shim", "cuda_fp16.h"),
             os.path.join(HERE, "ref_shim", "mma.h"), os.path.abspath(__file__)]
     if not force and os.path.exists(LIB) and os.path.exists(MANIFEST) and os.path.getmtime(LIB) >= max(os.path.getmtime(s) for s in srcs):

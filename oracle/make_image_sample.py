@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Builds samples/_generated/mlp_learning_an_image.hip: this repository's template (samples/mlp_learning_an_image.hip.in -- image IO, the
+"""Builds oracle/_ref/_generated/mlp_learning_an_image.hip: this repository's template (samples/mlp_learning_an_image.hip.in -- image IO, the
 bilinear lookup that stands where the CUDA texture stands, the PSNR report) with the REFERENCE'S OWN training loop spliced in, read from
 /root/reference/samples/mlp_learning_an_image.cu where it lies.  The point of the sample is that the reference's caller code compiles and
 runs unchanged against the facade headers (include/tiny-cuda-nn/*.h); the loop is therefore taken from the reference at build time, as
@@ -15,7 +15,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFERENCE = os.path.join(os.environ.get("REFERENCE_DIR", "/root/reference"), "samples", "mlp_learning_an_image.cu")
 TEMPLATE = os.path.join(ROOT, "samples", "mlp_learning_an_image.hip.in")
-OUT_DIR = os.path.join(ROOT, "samples", "_generated")
+OUT_DIR = os.path.join(ROOT, "oracle", "_ref", "_generated")  # made from the reference: with its other builds, never committed
 OUT = os.path.join(OUT_DIR, "mlp_learning_an_image.hip")
 
 

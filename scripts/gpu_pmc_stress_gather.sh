@@ -7,7 +7,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 cd /tmp
 run_pass () { local name=$1; shift
-  timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/pmc_$name -o pmc -- python $OLDPWD/bench.py --workload stress --steps 6 --warmup 2 --no-cpu-baseline --no-inference --dominant grid_forward > $OUT/pmc_$name.log 2>&1
+  timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/pmc_$name -o pmc -- python $OLDPWD/bench.py --full --workload stress --steps 6 --warmup 2 --no-cpu-baseline --no-inference --dominant grid_forward > $OUT/pmc_$name.log 2>&1
   echo "pass $name exit $?"; }
 run_pass fetch FETCH_SIZE
 run_pass tcc TCC_HIT_sum TCC_MISS_sum

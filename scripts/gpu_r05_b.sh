@@ -3,12 +3,12 @@
 # shipped config, the Adam layout microbenchmark, the torch binding's profile.
 OUT=$PWD/gpurun_out/r05b; mkdir -p $OUT
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
-for i in 1 2; do timeout 120 python bench.py --steps 200 --warmup 30 --no-cpu-baseline --api native --no-inference 2>$OUT/base_$i.err | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('base', round(d['ms_per_step'],4), 'resident', round(d.get('ms_per_step_resident',0),4), {k:round(v,4) for k,v in d['stages_ms'].items() if v>0})" >> $OUT/ab.txt 2>&1; done
+for i in 1 2; do timeout 120 python bench.py --full --steps 200 --warmup 30 --no-cpu-baseline --api native --no-inference 2>$OUT/base_$i.err | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('base', round(d['ms_per_step'],4), 'resident', round(d.get('ms_per_step_resident',0),4), {k:round(v,4) for k,v in d['stages_ms'].items() if v>0})" >> $OUT/ab.txt 2>&1; done
 for v in "2 0" "2 2" "4 2" "4 0"; do set -- $v
-  TCNN_BACKWARD_OVERLAP=$1 TCNN_BACKWARD_OVERLAP_LANES=$2 timeout 120 python bench.py --steps 200 --warmup 30 --no-cpu-baseline --api native --no-inference 2>$OUT/ov_$1_$2.err | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('overlap groups $1 lanes $2', round(d['ms_per_step'],4), 'resident', round(d.get('ms_per_step_resident',0),4), {k:round(v,4) for k,v in d['stages_ms'].items() if v>0})" >> $OUT/ab.txt 2>&1
+  TCNN_BACKWARD_OVERLAP=$1 TCNN_BACKWARD_OVERLAP_LANES=$2 timeout 120 python bench.py --full --steps 200 --warmup 30 --no-cpu-baseline --api native --no-inference 2>$OUT/ov_$1_$2.err | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('overlap groups $1 lanes $2', round(d['ms_per_step'],4), 'resident', round(d.get('ms_per_step_resident',0),4), {k:round(v,4) for k,v in d['stages_ms'].items() if v>0})" >> $OUT/ab.txt 2>&1
 done
 for m in bucketed sliced_f16 sliced_f32 atomic; do
-  TCNN_GRID_BACKWARD=$m timeout 120 python bench.py --workload hash_shipped --steps 200 --warmup 30 --no-cpu-baseline --api native --no-inference 2>$OUT/sh_$m.err | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('hash_shipped backward $m', round(d['ms_per_step'],4), 'resident', round(d.get('ms_per_step_resident',0),4), {k:round(v,4) for k,v in d['stages_ms'].items() if v>0})" >> $OUT/ab.txt 2>&1
+  TCNN_GRID_BACKWARD=$m timeout 120 python bench.py --full --workload hash_shipped --steps 200 --warmup 30 --no-cpu-baseline --api native --no-inference 2>$OUT/sh_$m.err | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('hash_shipped backward $m', round(d['ms_per_step'],4), 'resident', round(d.get('ms_per_step_resident',0),4), {k:round(v,4) for k,v in d['stages_ms'].items() if v>0})" >> $OUT/ab.txt 2>&1
 done
 cat $OUT/ab.txt
 timeout 300 scripts/microbench_adam_layout.bin > $OUT/microbench_adam_layout.txt 2>&1; cat $OUT/microbench_adam_layout.txt

@@ -9,7 +9,7 @@ done
 cat gpurun_out/ab/log.txt; cp gpurun_out/ab/log.txt $OUT/sweep.txt
 cd /tmp
 for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "tcc TCC_HIT_sum TCC_MISS_sum"; do set -- $pass; name=$1; shift
-  timeout 600 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/pmc_$name -o pmc -- python $OLDPWD/bench.py --workload stress --steps 6 --warmup 2 --no-cpu-baseline --no-inference --api native --dominant adam > $OUT/pmc_$name.log 2>&1
+  timeout 600 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/pmc_$name -o pmc -- python $OLDPWD/bench.py --full --workload stress --steps 6 --warmup 2 --no-cpu-baseline --no-inference --api native --dominant adam > $OUT/pmc_$name.log 2>&1
   echo "stress pass $name exit $?"
 done
 cd $OLDPWD

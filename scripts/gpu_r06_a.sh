@@ -12,21 +12,21 @@ done
 unset TCNN_HIP_LIBRARY
 for v in r05 default; do
   if [ $v = r05 ]; then export TCNN_HIP_LIBRARY=$PWD/tiny-cuda-nn_amd/lib/variants/r05.so; else unset TCNN_HIP_LIBRARY; fi
-  timeout 120 python bench.py --workload mlp --steps 100 --warmup 20 --no-cpu-baseline --api native 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('mlp $v', round(d['ms_per_step'],4), {k:round(x,4) for k,x in d['stages_ms'].items() if x>0})" >> gpurun_out/ab/log.txt 2>&1
-  timeout 200 python bench.py --workload stress --steps 30 --warmup 10 --no-cpu-baseline --api native 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('stress $v', round(d['ms_per_step'],4), {k:round(x,4) for k,x in d['stages_ms'].items() if x>0})" >> gpurun_out/ab/log.txt 2>&1
+  timeout 120 python bench.py --full --workload mlp --steps 100 --warmup 20 --no-cpu-baseline --api native 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('mlp $v', round(d['ms_per_step'],4), {k:round(x,4) for k,x in d['stages_ms'].items() if x>0})" >> $(dirname $OUT)/ab/log.txt 2>&1
+  timeout 200 python bench.py --full --workload stress --steps 30 --warmup 10 --no-cpu-baseline --api native 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('stress $v', round(d['ms_per_step'],4), {k:round(x,4) for k,x in d['stages_ms'].items() if x>0})" >> $(dirname $OUT)/ab/log.txt 2>&1
 done
 unset TCNN_HIP_LIBRARY
 cp gpurun_out/ab/log.txt $OUT/ab_log.txt; cat $OUT/ab_log.txt
 # kernel trace of the new library
-( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o trace -- python $OLDPWD/bench.py --steps 50 --warmup 10 --no-cpu-baseline --api native > $OUT/rocprof.log 2>&1 )
+( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o trace -- python $OLDPWD/bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --api native > $OUT/rocprof.log 2>&1 )
 for f in $(find $OUT/prof -name "*kernel_stats.csv"); do cp $f $OUT/kernel_stats.csv; cut -c1-150 $f | head -12; done
 find $OUT/prof -name "*kernel_trace.csv" -delete; find $OUT/prof -name "*.db" -delete
 # SQ counters, new and base
 cd /tmp
 for v in new r05; do
   if [ $v = r05 ]; then export TCNN_HIP_LIBRARY=$OLDPWD/tiny-cuda-nn_amd/lib/variants/r05.so; else unset TCNN_HIP_LIBRARY; fi
-  timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES --kernel-trace --output-format csv -d $OUT/$v/pmc_sq -o pmc -- python $OLDPWD/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-inference --api native > $OUT/pmc_sq_$v.log 2>&1
-  timeout 300 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU --kernel-trace --output-format csv -d $OUT/$v/pmc_wait -o pmc -- python $OLDPWD/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-inference --api native > $OUT/pmc_wait_$v.log 2>&1
+  timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES --kernel-trace --output-format csv -d $OUT/$v/pmc_sq -o pmc -- python $OLDPWD/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-inference --api native > $OUT/pmc_sq_$v.log 2>&1
+  timeout 300 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU --kernel-trace --output-format csv -d $OUT/$v/pmc_wait -o pmc -- python $OLDPWD/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-inference --api native > $OUT/pmc_wait_$v.log 2>&1
 done
 unset TCNN_HIP_LIBRARY
 cd $OLDPWD

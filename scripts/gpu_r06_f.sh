@@ -7,5 +7,5 @@ echo "bf16 rc=$? $(grep -E 'passed|failed' $OUT/pytest_bf16.log | tail -1)"; gre
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_parity_full.py -m gpu -x -q -k "bucket or grid or backward or headline or owner or stress" > $OUT/pytest_grid.log 2>&1
 echo "fp16 grid rc=$? $(grep -E 'passed|failed' $OUT/pytest_grid.log | tail -1)"
 for p in fp16 bf16; do for w in stress hash; do
-  timeout 200 python bench.py --workload $w --precision $p --steps 30 --warmup 10 --no-cpu-baseline --api native 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$w $p', round(d['ms_per_step'],4), {k:round(v,4) for k,v in d['stages_ms'].items() if v>0}, 'wide slices', d.get('grid_owner_wide_slices'))"
+  timeout 200 python bench.py --full --workload $w --precision $p --steps 30 --warmup 10 --no-cpu-baseline --api native 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$w $p', round(d['ms_per_step'],4), {k:round(v,4) for k,v in d['stages_ms'].items() if v>0}, 'wide slices', d.get('grid_owner_wide_slices'))"
 done; done 2>&1 | tee $OUT/bench.txt

@@ -12,6 +12,6 @@ cp gpurun_out/ab/log.txt $OUT/ab_log.txt; sort $OUT/ab_log.txt | cut -c1-260
 cd /tmp
 for v in wave4 base; do
   if [ $v = base ]; then unset TCNN_HIP_LIBRARY; else export TCNN_HIP_LIBRARY=/root/repo/tiny-cuda-nn_amd/lib/variants/$v.so; fi
-  rocprofv3 --kernel-trace --stats -d $OUT/prof_$v -o p -- python /root/repo/bench.py --steps 100 --warmup 20 --no-cpu-baseline --api native > $OUT/rocprof_$v.log 2>&1
+  rocprofv3 --kernel-trace --stats -d $OUT/prof_$v -o p -- python $OLDPWD/bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --api native > $OUT/rocprof_$v.log 2>&1
   f=$(find $OUT/prof_$v -name "*kernel_stats.csv" | head -1); echo "== $v"; head -8 $f | cut -c1-60,150-260
 done

@@ -22,6 +22,7 @@ from test_gpu_parity import positions, targets_for, tcnn
 pytestmark = pytest.mark.gpu
 
 DRIVER_COMMAND = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"]
+FULL_COMMAND = DRIVER_COMMAND + ["--full"]  # everything besides the headline figure: roofline, breakdown, inference, binding, CPU baseline
 
 
 def _run(cmd, **env):
@@ -39,12 +40,37 @@ def r_adam_moved(d):
     return "moved_frac" not in st or (0.0 < st["moved_frac"] < 1.2 and st["moved_bytes_per_launch"] > 0)
 
 
+def test_plain_bench_command_dumps_its_outputs_in_fresh_processes(tmp_path):
+    """The plain driver command -- `python3 bench.py --gpus 1 --steps 20 --warmup 5` -- twice, each in a process of its own, with
+    --dump-outputs: one JSON line with the contract's fields and nothing of --full's; the last timed step's outputs as float32 .npy
+    files, within 64 MB, from the same inputs in both processes."""
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d = _run(DRIVER_COMMAND + ["--dump-outputs", str(out)])
+        assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "samples/s" and d["higher_is_better"] is True
+        assert d["full"] is False and d["protocol"]["timed_steps"] == 20 and "f16" in d["dtype"] and "samples/s" in d["metric"]
+        assert abs(d["value"] - (1 << 18) / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert not {"roofline", "stages_ms", "cpu_baseline", "inference", "torch_binding", "value_resident", "final_loss", "attempts"} & set(d), sorted(d)
+        files = {p.stem: np.load(p) for p in out.glob("*.npy")}
+        assert set(files) == set(d["outputs_dumped"]) and all(list(a.shape) == d["outputs_dumped"][k] for k, a in files.items())
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert files["inference_last_batch"].shape == (1 << 18, 4) and files["last_batch_input"].shape == (1 << 18, 3)
+        dumps.append(files)
+    for k in ("last_batch_input", "last_batch_target"):  # same arguments, same inputs: bit for bit
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    # training is not bitwise reproducible from run to run: the predictions agree with a tolerance (2.5 % after 1000 headline steps)
+    a, b = (d["inference_last_batch"].astype(np.float64) for d in dumps)
+    assert np.linalg.norm(a - b) <= 0.1 * np.linalg.norm(a)
+
+
 def test_driver_bench_command_in_fresh_processes():
-    """`python3 bench.py --gpus 1 --steps 20 --warmup 5`, three times, each in a process of its own: exit code 0, one JSON line
+    """The driver's command with --full, `python3 bench.py --gpus 1 --steps 20 --warmup 5 --full`, three times, each in a process of its own: exit code 0, one JSON line
     with the contract's fields, `roofline` and `cpu_baseline` present, a loss that went down, no faulted worker."""
     values = []
     for _ in range(3):
-        d = _run(DRIVER_COMMAND, TCNN_BENCH_CPU_BUDGET_S="2")  # the CPU leg is bounded at 2 s here (12 s by default)
+        d = _run(FULL_COMMAND, TCNN_BENCH_CPU_BUDGET_S="2")  # the CPU leg is bounded at 2 s here (12 s by default)
         assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "samples/s" and d["higher_is_better"] is True
         assert d["attempts"] == 1 and d["faulted"] is False and "faulted_attempts" not in d
         # the reference's protocol (samples/mlp_learning_an_image.cu:263-271): the batch is drawn and its target evaluated inside every
@@ -100,7 +126,7 @@ def test_driver_multi_gpu_command_with_two_ranks_on_one_gpu(dp):
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2"] + (["--dp", dp] if dp else [])
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full"] + (["--dp", dp] if dp else [])
     d = _run(cmd, TCNN_BENCH_BACKEND="gloo", TCNN_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     assert d["n_gpus"] == 2 and d["steps"] == 6 and d["warmup"] == 2 and d["scaling"] == "weak"
     if dp is None:
@@ -119,7 +145,7 @@ def test_driver_multi_gpu_command_with_two_ranks_on_one_gpu(dp):
 
 def test_bench_other_workloads_print_their_line():
     for workload, kernel in (("mlp", "mlp_train_fused"), ("stress", "adam"), ("hash_shipped", None)):
-        d = _run(DRIVER_COMMAND + ["--workload", workload, "--no-cpu-baseline"])
+        d = _run(FULL_COMMAND + ["--workload", workload, "--no-cpu-baseline"])
         if workload == "hash_shipped":  # data/config_hash.json as the reference ships it (2-D -> 3, T = 2^15): the one configuration it publishes a figure for
             assert d["config"]["n_params"] == 708368 + 7168 and "2D->3" in d["config"]["workload"]  # SURVEY 8 (derived sizes)
             v = d["vs_reference_readme"]
@@ -145,7 +171,7 @@ def test_bench_launches_its_own_ranks_when_no_launcher_is_around_it():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     for dp, phases in (("sharded", {"reduce_scatter", "adam_shard", "all_gather"}),
                        ("direct", {"signal+wait_gradients", "reduce", "adam_shard", "push", "signal+wait_parameters"})):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--dp", dp]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--dp", dp]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT,
                            env=dict(env, TCNN_BENCH_BACKEND="gloo", TCNN_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0"))
         assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -162,7 +188,7 @@ def test_bench_launches_its_own_ranks_when_no_launcher_is_around_it():
 
 
 def test_bench_resident_batches_on_request():
-    d = _run(DRIVER_COMMAND + ["--no-regenerate", "--no-cpu-baseline", "--no-inference"])
+    d = _run(FULL_COMMAND + ["--no-regenerate", "--no-cpu-baseline", "--no-inference"])
     assert d["protocol"]["regenerate"] is False and "value_resident" not in d and "inference" not in d and math.isfinite(d["final_loss"])
 
 
@@ -184,7 +210,7 @@ def test_bench_steps_under_the_checking_allocator(mode):
     an access past a block's end faults (the worker would die, attempts > 1 or a non-zero exit); `canary` -- a write outside a
     block fails debug_check_allocations() at the end of the run.  Blocks are poisoned, recycled ones afresh: nothing may depend
     on what an earlier use of a scratch block left behind."""
-    d = _run(DRIVER_COMMAND + ["--no-cpu-baseline"], TCNN_DEBUG_ALLOC=mode)
+    d = _run(FULL_COMMAND + ["--no-cpu-baseline"], TCNN_DEBUG_ALLOC=mode)
     assert d["attempts"] == 1 and math.isfinite(d["final_loss"]) and d["final_loss"] < 0.5
 
 
@@ -309,7 +335,7 @@ def test_multi_gpu_auto_falls_back_to_the_collectives_when_the_direct_exchange_i
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full"]
     d = _run(cmd, TCNN_BENCH_BACKEND="gloo", TCNN_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", TCNN_DEBUG_ALLOC="canary")
     a = d["dp_autotune"]
     assert a["chosen"] == "sharded" and "sharded" in d["config"]["parallelism"]

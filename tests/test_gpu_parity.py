@@ -1266,14 +1266,16 @@ def test_grid_second_order_beyond_the_bucket_limits():
 
 def test_cpp_sample_learns_an_image(tmp_path):
     """The reference's demo (samples/mlp_learning_an_image.cu: its training loop is spliced from /root/reference into this repository's
-    template at build time, samples/make_image_sample.py; the binary travels) against the C++ facade: 2-D hash grid + MLP learn a test card from random pixel
-    lookups drawn by the library's pcg32 kernel; the rendered image reaches a PSNR that only a working training path gives."""
+    template at build time by oracle/make_image_sample.py and oracle/Makefile; source and binary land in oracle/_ref/ and travel) against the C++ facade:
+    2-D hash grid + MLP learn a test card from random pixel lookups drawn by the library's pcg32 kernel; the rendered image reaches a PSNR that
+    only a working training path gives."""
     import subprocess
-    exe = os.path.join(ROOT, "samples", "mlp_learning_an_image")
+    from oracle import build_ref
+    exe = build_ref.IMAGE
     if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "samples"), "-s"])
+        build_ref.build(verbose=False)  # builds it where the reference tree is present
     if not os.path.exists(exe):
-        pytest.skip("the sample's source is generated from /root/reference at build time (samples/make_image_sample.py); neither it nor a prebuilt binary is here")
+        pytest.skip("the sample is generated from the reference tree at build time (oracle/make_image_sample.py); neither that tree nor a prebuilt binary is here")
     r = subprocess.run([exe, "-", "-", "300"], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout + r.stderr
     psnr = float(r.stdout.split("psnr=")[1].split()[0])
