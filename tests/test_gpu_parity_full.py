@@ -184,7 +184,7 @@ def test_adam_bit_level_in_both_step_counter_forms(l2_reg, clip):
     assert n == md.n_params
     st = O.TrainState(md, tm.params_full_precision.cpu().numpy())
     rng = np.random.default_rng(3)
-    # global batch -> representation (api.hip choose_step_representation): 1 sample keeps counters, 2^20 samples deficits
+    # global batch -> representation (trainer_optimizer.hip choose_step_representation): 1 sample keeps counters, 2^20 samples deficits
     schedule = [1, 1, 1 << 20, 1 << 20, 1 << 20, 1, 1, 1 << 20]
     for k, batch in enumerate(schedule):
         g = (rng.standard_normal(n) * rng.choice([1e-3, 1.0, 60.0], n)).astype(np.float16)
@@ -208,7 +208,7 @@ def test_adam_bit_level_in_both_step_counter_forms(l2_reg, clip):
 
 
 def test_adam_byte_deficits_beyond_254_skipped_steps():
-    """The step-counter deficits kept as bytes (api.hip choose_step_representation; elementwise_kernels.h AdamStepsForm): entries that are
+    """The step-counter deficits kept as bytes (trainer_optimizer.hip choose_step_representation; elementwise_kernels.h AdamStepsForm): entries that are
     skipped more than 254 times in a row move into the 32-bit counter array (byte 255) and keep their exact count -- 300 optimizer steps on
     the GPU against the oracle's counters, with a snapshot (which converts to counters and back) in the middle."""
     T = tcnn()

@@ -1,0 +1,245 @@
+// api_module.hip -- C ABI: the type-erased Module (tcnn_module_*; reference src/cpp_api.cu:72-174) over model_desc / model_exec.
+#include <algorithm>
+#include <memory>
+#include <string>
+
+#include "host_common.h"
+#include "model_exec.h"
+#include "switches.h"
+
+using namespace tcnn_hip;
+
+struct tcnn_module {
+	Model md;
+	std::string name;
+	uint32_t lds_level_budget = 0;  // 0: default LDS slice size of the sliced grid backward
+	// create_encoding(..., Precision::Fp32) (cpp_api.cu:165-174 -> Encoding<float>): parameters, outputs and gradients are fp32 and the
+	// first-order passes COMPUTE in fp32 (encoding_forward_f32 / encoding_backward_f32: the grid's kernel_grid<float> formulation, fp32
+	// global atomics for its parameter gradients; frequency / one-blob / identity with float values).  Only the second-order pass
+	// (backward_backward_input, grid only) still goes through 16-bit stand-ins of the caller's tensors: incoming gradients are scaled
+	// into that type's range by the largest power of two <= FP32_GRADIENT_SCALE that keeps max |dL_doutput| * scale <=
+	// FP32_GRADIENT_TARGET (found on the device per call) and the results scaled back, exactly.
+	bool fp32_io = false;
+};
+static constexpr float FP32_GRADIENT_SCALE = 1024.0f, FP32_GRADIENT_TARGET = 16384.0f;
+// the 16-bit copies an fp32 module works on
+struct Fp32Bridge {
+	Scratch params, output, dL_doutput, dL_dparams;
+	static Scratch to_half(hipStream_t stream, const void* src, size_t n, float scale = 1.0f) {
+		Scratch s(stream, std::max<size_t>(n, 1) * sizeof(half_t));
+		cast_scaled_f32_to_f16(stream, n, (const float*)src, s.as<half_t>(), scale);
+		return s;
+	}
+	// the gradient entering the backward pass: scaled by a per-call power of two left in `scale_pair` ({scale, 1 / scale} on the device)
+	static Scratch gradient_to_half(hipStream_t stream, const void* src, size_t n, Scratch& scale_pair) {
+		scale_pair = Scratch(stream, 4 * sizeof(float));
+		gradient_scale_from_absmax(stream, n, (const float*)src, scale_pair.as<float>(), FP32_GRADIENT_SCALE, FP32_GRADIENT_TARGET);
+		Scratch s(stream, std::max<size_t>(n, 1) * sizeof(half_t));
+		cast_scaled_f32_to_f16(stream, n, (const float*)src, s.as<half_t>(), (const float*)scale_pair.as<float>());
+		return s;
+	}
+};
+struct tcnn_context {
+	ForwardCtx ctx;
+};
+
+extern "C" {
+
+int tcnn_create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json, const char* network_json,
+                                            tcnn_module_t** out) {
+	TCNN_API_BEGIN
+	auto m = std::make_unique<tcnn_module>();
+	m->md = make_nwie(n_input_dims, n_output_dims, Json::parse(encoding_json), Json::parse(network_json));
+	m->name = m->md.name();
+	*out = m.release();
+	TCNN_API_END
+}
+
+int tcnn_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json, tcnn_module_t** out) {
+	return tcnn_create_network_with_input_encoding(n_input_dims, n_output_dims, "{\"otype\": \"Identity\"}", network_json, out);  // cpp_api.cu:160-162
+}
+
+int tcnn_create_encoding(uint32_t n_input_dims, const char* encoding_json, int requested_precision, tcnn_module_t** out) {
+	TCNN_API_BEGIN
+	if (requested_precision != NATIVE_PRECISION && requested_precision != TCNN_PRECISION_FP32) {
+		set_last_error(HALF_IS_BF16 ? "create_encoding: this build (libtcnn_hip_bf16.so) provides bf16 and fp32 encodings"
+		                            : "create_encoding: this build provides fp16 and fp32 encodings");
+		return TCNN_ERROR_UNSUPPORTED;
+	}
+	auto m = std::make_unique<tcnn_module>();
+	m->fp32_io = requested_precision == TCNN_PRECISION_FP32;
+	m->md.n_input_dims = n_input_dims;
+	m->md.enc = create_encoding_desc(n_input_dims, Json::parse(encoding_json), /*alignment=*/0);  // cpp_api.cu:165-174
+	m->md.has_network = false;
+	m->md.finish();
+	m->name = m->md.name();
+	*out = m.release();
+	TCNN_API_END
+}
+
+void tcnn_module_destroy(tcnn_module_t* m) { delete m; }
+
+int tcnn_module_inference(tcnn_module_t* m, tcnn_stream_t stream_, uint32_t n, const float* input, void* output, void* params) {
+	TCNN_API_BEGIN
+	hipStream_t stream = (hipStream_t)stream_;
+	if (m->fp32_io) {
+		encoding_forward_f32(stream, m->md, IoLayout::dense(m->md), n, input, (const float*)params, (float*)output, nullptr, false);
+		return TCNN_OK;
+	}
+	model_forward(stream, nullptr, m->md, IoLayout::dense(m->md), n, input, (half_t*)output, (const half_t*)params, nullptr, false);
+	TCNN_API_END
+}
+
+int tcnn_module_forward(tcnn_module_t* m, tcnn_stream_t stream_, uint32_t n, const float* input, void* output, void* params,
+                        int prepare_input_gradients, tcnn_context_t** ctx) {
+	TCNN_API_BEGIN
+	hipStream_t stream = (hipStream_t)stream_;
+	auto c = std::make_unique<tcnn_context>();
+	if (m->fp32_io) {
+		encoding_forward_f32(stream, m->md, IoLayout::dense(m->md), n, input, (const float*)params, (float*)output, &c->ctx, prepare_input_gradients != 0);
+	} else {
+		model_forward(stream, nullptr, m->md, IoLayout::dense(m->md), n, input, (half_t*)output, (const half_t*)params, &c->ctx, prepare_input_gradients != 0);
+	}
+	*ctx = c.release();
+	TCNN_API_END
+}
+
+int tcnn_module_backward(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_context_t* ctx, uint32_t n, float* dL_dinput, const void* dL_doutput,
+                         void* dL_dparams, const float* input, const void* output, const void* params) {
+	(void)output;
+	TCNN_API_BEGIN
+	if (!ctx) throw std::runtime_error("backward: missing forward context");
+	if (m->fp32_io) {  // bare encodings only: neither `output` nor the parameters are needed by their first-order backward pass
+		(void)params;
+		encoding_backward_f32((hipStream_t)stream, m->md, IoLayout::dense(m->md), ctx->ctx, n, dL_dinput, (const float*)dL_doutput, (float*)dL_dparams, input);
+		return TCNN_OK;
+	}
+	model_backward((hipStream_t)stream, nullptr, m->md, IoLayout::dense(m->md), ctx->ctx, n, dL_dinput, (const half_t*)dL_doutput, (half_t*)dL_dparams, input, (const half_t*)output,
+	               (const half_t*)params,
+	               dL_dparams ? TCNN_GRADIENT_OVERWRITE : TCNN_GRADIENT_IGNORE, m->lds_level_budget);  // cpp_api.cu:115
+	TCNN_API_END
+}
+
+// cpp_api.cu:117-135 -> DifferentiableObject::backward_backward_input, implemented by the grid encoding only in the
+// reference (grid.h:910-1042; object.h:468 throws for everything else).
+int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_, const tcnn_context_t* ctx, uint32_t n, const float* dL_ddLdinput,
+                                        const float* input, const void* dL_doutput, void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput,
+                                        const void* params) {
+	if (m->md.has_network || !m->md.enc.is_grid) {
+		set_last_error("DifferentiableObject::backward_backward_input_impl: not implemented error");  // object.h:478
+		return TCNN_ERROR_UNSUPPORTED;
+	}
+	TCNN_API_BEGIN
+	if (!ctx) throw std::runtime_error("backward_backward_input: missing forward context");
+	check_batch(n, widest_matrix(m->md));
+	if (n == 0) return TCNN_OK;
+	if (ctx->ctx.n != n) throw std::runtime_error("backward_backward_input: batch size does not match the forward context");
+	if (!dL_ddLdinput) throw std::runtime_error("backward_backward_input: dL_ddLdinput is required");
+	hipStream_t stream = (hipStream_t)stream_;
+	const Model& md = m->md;
+	const EncodingDesc& e = md.enc;
+	// fp32 module: 16-bit stand-ins for the caller's fp32 tensors (see tcnn_module::fp32_io)
+	Scratch dy16, p16, dp16, ddy16, gscale;
+	void* const dL_dparams_f32 = dL_dparams;
+	void* const dL_ddLdoutput_f32 = dL_ddLdoutput;
+	const size_t n_out_elems = (size_t)n * e.padded_output_width;
+	if (m->fp32_io) {
+		if (dL_doutput) {
+			dy16 = Fp32Bridge::gradient_to_half(stream, dL_doutput, n_out_elems, gscale);
+			dL_doutput = dy16.ptr;
+		}
+		if (params) {
+			p16 = Fp32Bridge::to_half(stream, params, md.n_params());
+			params = p16.ptr;
+		}
+		if (dL_dparams) {
+			dp16 = Scratch(stream, std::max<size_t>(md.n_params(), 1) * sizeof(half_t));
+			dL_dparams = dp16.ptr;
+		}
+		if (dL_ddLdoutput) {
+			ddy16 = Scratch(stream, std::max<size_t>(n_out_elems, 1) * sizeof(half_t));
+			dL_ddLdoutput = ddy16.ptr;
+		}
+	}
+	GridIO io = {input, md.n_input_dims, 1u, n, 1u, e.padded_output_width};  // the bare encoding's output is sample-major (cpp_api.cu:94-95)
+	io.ddx = dL_ddLdinput;
+	io.ddx_stride_i = md.n_input_dims;
+	io.ddx_stride_d = 1u;
+	if (dL_ddLdoutput) {  // grid.h:1012-1035
+		if (!ctx->ctx.dy_dx.ptr) throw std::runtime_error("backward_backward_input: the forward pass did not prepare input gradients");
+		grid_backward_backward_dLdoutput(stream, md.n_input_dims, e.n_output_dims, e.padded_output_width - e.n_output_dims, io, ctx->ctx.dy_dx.as<float>(),
+		                                 (half_t*)dL_ddLdoutput);
+	}
+	if (dL_dparams || dL_dinput) {
+		if (!dL_doutput) throw std::runtime_error("backward_backward_input: dL_doutput is required for parameter / input gradients");
+	}
+	if (dL_dparams && e.n_params > 0) {  // grid.h:942-975, GradientMode::Overwrite
+		uint32_t budget = m->lds_level_budget ? m->lds_level_budget : g_default_lds_slice_bytes;
+		GridBackwardWorkspace ws = grid_backward_workspace_size(e.grid, n, GridBackwardMode::Bucketed, budget);
+		Scratch queues;
+		if (ws.scratch_bytes) {
+			queues = Scratch(stream, ws.scratch_bytes);
+			ws.scratch = queues.ptr;
+			ws.scratch_bytes = queues.bytes;
+			ws.counters = ZeroedCounters::get(stream, ws.n_counters);
+		}
+		grid_backward(stream, e.grid, io, (const half_t*)dL_doutput, (half_t*)dL_dparams, false, GridBackwardMode::Bucketed, budget, ws);
+	}
+	if (dL_dinput) {  // grid.h:977-1010
+		grid_backward_backward_input(stream, e.grid, io, (const half_t*)dL_doutput, (const half_t*)params, dL_dinput, md.n_input_dims, 1u);
+	}
+	if (m->fp32_io) {  // dL_ddLdoutput does not depend on dL_doutput; the other two carry its scale
+		if (dL_ddLdoutput_f32) cast_f16_to_f32(stream, n_out_elems, ddy16.as<half_t>(), (float*)dL_ddLdoutput_f32);
+		if (dL_dparams_f32) {
+			if (gscale.ptr) cast_scaled_f16_to_f32(stream, md.n_params(), dp16.as<half_t>(), (float*)dL_dparams_f32, (const float*)(gscale.as<float>() + 1));
+			else cast_f16_to_f32(stream, md.n_params(), dp16.as<half_t>(), (float*)dL_dparams_f32);
+		}
+		if (dL_dinput && gscale.ptr) scale_f32(stream, (size_t)n * md.n_input_dims, dL_dinput, (const float*)(gscale.as<float>() + 1));
+	}
+	TCNN_API_END
+}
+void tcnn_context_destroy(tcnn_context_t* ctx) { delete ctx; }
+
+uint32_t tcnn_module_n_input_dims(const tcnn_module_t* m) { return m->md.n_input_dims; }
+uint32_t tcnn_module_n_output_dims(const tcnn_module_t* m) { return m->md.padded_output_width(); }
+size_t tcnn_module_n_params(const tcnn_module_t* m) { return m->md.n_params(); }
+int tcnn_module_param_precision(const tcnn_module_t* m) { return m->fp32_io ? TCNN_PRECISION_FP32 : NATIVE_PRECISION; }
+int tcnn_module_output_precision(const tcnn_module_t* m) { return m->fp32_io ? TCNN_PRECISION_FP32 : NATIVE_PRECISION; }
+
+int tcnn_module_initialize_params(tcnn_module_t* m, size_t seed, float* params_full_precision, float scale) {
+	TCNN_API_BEGIN
+	Pcg32 rng{(uint64_t)seed};  // cpp_api.cu:139-142
+	m->md.initialize_params(nullptr, rng, params_full_precision, scale);
+	HIP_CHECK(hipStreamSynchronize(nullptr));
+	TCNN_API_END
+}
+
+const char* tcnn_module_hyperparams_json(const tcnn_module_t* m) { return m->md.hyper_json.c_str(); }
+const char* tcnn_module_name(const tcnn_module_t* m) { return m->name.c_str(); }
+int tcnn_module_jit_fusion(const tcnn_module_t*) { return 0; }
+int tcnn_module_set_jit_fusion(tcnn_module_t*, int val) {
+	if (val) log_message(TCNN_LOG_WARNING, "JIT fusion was requested but this build has no runtime compilation path; the statically fused kernels are used.");
+	return TCNN_OK;
+}
+
+int tcnn_module_grid_indices(tcnn_module_t* m, tcnn_stream_t stream, uint32_t n, const float* input, uint32_t* indices) {
+	TCNN_API_BEGIN
+	if (!m->md.enc.is_grid) throw std::runtime_error("grid_indices: module has no grid encoding");
+	GridIO io = {input, m->md.n_input_dims, 1u, n, n, 1u};
+	grid_indices((hipStream_t)stream, m->md.enc.grid, io, indices);
+	TCNN_API_END
+}
+int tcnn_module_grid_level_n_params(const tcnn_module_t* m, uint32_t level, size_t* out) {
+	TCNN_API_BEGIN
+	if (!m->md.enc.is_grid || level >= m->md.enc.grid.n_levels) throw std::runtime_error("grid_level_n_params: invalid level");
+	*out = m->md.enc.grid.offset[level + 1] - m->md.enc.grid.offset[level];  // multi_level_interface.h level_n_params
+	TCNN_API_END
+}
+int tcnn_module_grid_level_params_offset(const tcnn_module_t* m, uint32_t level, size_t* out) {
+	TCNN_API_BEGIN
+	if (!m->md.enc.is_grid || level >= m->md.enc.grid.n_levels) throw std::runtime_error("grid_level_params_offset: invalid level");
+	*out = m->md.enc.grid.offset[level];
+	TCNN_API_END
+}
+
+}  // extern "C"

@@ -1,0 +1,308 @@
+// model_desc.hip -- JSON -> model description factories, enum <-> string tables, hyper-parameter JSON, parameter initialisation.
+#include "model_desc.h"
+
+#include <cmath>
+#include <limits>
+#include <vector>
+
+#include "host_common.h"
+
+namespace tcnn_hip {
+
+// ------------------------------------------------------------------------------------------------
+// model description
+// ------------------------------------------------------------------------------------------------
+static uint32_t powi(uint32_t base, uint32_t exponent) {
+	uint32_t r = 1;
+	for (uint32_t i = 0; i < exponent; ++i) r *= base;
+	return r;
+}
+
+static const char* to_string(GridType t) { return t == GridType::Hash ? "Hash" : t == GridType::Dense ? "Dense" : "Tiled"; }
+static const char* to_string(InterpolationType t) {
+	return t == InterpolationType::Nearest ? "Nearest" : t == InterpolationType::Linear ? "Linear" : "Smoothstep";
+}
+static const char* const ACTIVATION_NAMES[] = {"None", "ReLU", "LeakyReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus", "Tanh"};
+static const char* to_string(Activation a) { return ACTIVATION_NAMES[(int)a]; }
+
+static GridType string_to_grid_type(const std::string& s) {  // common_host.cu:112-122
+	if (equals_case_insensitive(s, "Hash")) return GridType::Hash;
+	if (equals_case_insensitive(s, "Dense")) return GridType::Dense;
+	if (equals_case_insensitive(s, "Tiled") || equals_case_insensitive(s, "Tile")) return GridType::Tiled;
+	throw std::runtime_error("Invalid grid type: " + s);
+}
+static InterpolationType string_to_interpolation_type(const std::string& s) {  // common_host.cu:160-170
+	if (equals_case_insensitive(s, "Nearest")) return InterpolationType::Nearest;
+	if (equals_case_insensitive(s, "Linear")) return InterpolationType::Linear;
+	if (equals_case_insensitive(s, "Smoothstep")) return InterpolationType::Smoothstep;
+	throw std::runtime_error("Invalid interpolation type: " + s);
+}
+static Activation string_to_activation(const std::string& s) {  // common_host.cu:70-96
+	for (int i = 0; i < 8; ++i) {
+		if (equals_case_insensitive(s, ACTIVATION_NAMES[i])) return (Activation)i;
+	}
+	// SiLU and Sine need stored pre-activations, which FullyFusedMLP does not keep (common_device.h:377-386)
+	if (equals_case_insensitive(s, "SiLU") || equals_case_insensitive(s, "Sine")) {
+		throw std::runtime_error("Activation '" + s + "' is not supported by FullyFusedMLP (it needs stored pre-activations).");
+	}
+	throw std::runtime_error("Invalid activation name: " + s);  // common_host.cu:94
+}
+
+void EncodingDesc::set_alignment(uint32_t alignment) {
+	uint32_t a = alignment, b = required_output_alignment();
+	uint32_t x = a, y = b;
+	while (y) {
+		uint32_t t = x % y;
+		x = y;
+		y = t;
+	}
+	const uint32_t l = a / x * b;
+	padded_output_width = next_multiple(n_output_dims, l);
+}
+
+Json EncodingDesc::hyperparams() const {
+	Json j = Json::object();
+	if (is_grid) {  // grid.h:1115-1132
+		j["otype"] = "Grid";
+		j["type"] = to_string((GridType)grid.grid_type);
+		j["n_levels"] = grid.n_levels;
+		j["n_features_per_level"] = grid.n_feat;
+		j["base_resolution"] = base_resolution;
+		j["per_level_scale"] = per_level_scale;
+		j["interpolation"] = to_string((InterpolationType)grid.interp);
+		j["hash"] = "CoherentPrime";
+		if ((GridType)grid.grid_type == GridType::Hash) j["log2_hashmap_size"] = log2_hashmap_size;
+	} else if (is_frequency) {  // frequency.h:200-205
+		j["otype"] = "Frequency";
+		j["n_frequencies"] = n_frequencies;
+	} else if (is_oneblob) {  // oneblob.h:296-301
+		j["otype"] = "OneBlob";
+		j["n_bins"] = n_bins;
+	} else {
+		j["otype"] = "Identity";
+		j["scale"] = id_scale;
+		j["offset"] = id_offset;
+	}
+	return j;
+}
+
+static EncodingDesc create_grid_encoding(uint32_t n_dims, const Json& enc) {  // grid.h:1725-1852
+	EncodingDesc e;
+	e.is_grid = true;
+	e.n_dims = n_dims;
+	const std::string hash = enc.value("hash", "CoherentPrime");
+	if (!equals_case_insensitive(hash, "CoherentPrime")) throw std::runtime_error("GridEncoding: compiled without " + hash + " hash support.");
+	const uint32_t F = enc.value("n_features_per_level", 2u);
+	if (F != 1 && F != 2 && F != 4 && F != 8) throw std::runtime_error("GridEncoding: n_features_per_level must be 1, 2, 4, or 8.");
+	const uint32_t log2_hashmap_size = enc.value("log2_hashmap_size", 19u);
+	const std::string otype = enc.value("otype", "Grid");
+	const std::string default_type = equals_case_insensitive(otype, "TiledGrid") ? "Tiled" : (equals_case_insensitive(otype, "DenseGrid") ? "Dense" : "Hash");
+	uint32_t n_features;
+	if (enc.contains("n_features") || enc.contains("n_grid_features")) {
+		n_features = (uint32_t)(enc.contains("n_features") ? enc["n_features"] : enc["n_grid_features"]).as_number();
+		if (enc.contains("n_levels")) throw std::runtime_error("GridEncoding: may not specify n_features and n_levels simultaneously (one determines the other)");
+	} else {
+		n_features = F * enc.value("n_levels", 16u);
+	}
+	const uint32_t n_levels = n_features / F;
+	const GridType grid_type = string_to_grid_type(enc.value("type", default_type));
+	const uint32_t base_resolution = enc.value("base_resolution", 16u);
+	const float default_scale = grid_type == GridType::Dense ? std::exp(std::log(256.0f / (float)base_resolution) / (float)(n_levels - 1)) : 2.0f;
+	const float per_level_scale = enc.value("per_level_scale", default_scale);
+
+	const InterpolationType interp = string_to_interpolation_type(enc.value("interpolation", "Linear"));
+	if (n_dims < 2 || n_dims > 4) throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4.");
+	if (n_levels > MAX_N_LEVELS) throw std::runtime_error("GridEncoding: m_n_levels=" + std::to_string(n_levels) + " must be at most MAX_N_LEVELS=" + std::to_string(MAX_N_LEVELS));
+	if (n_features % F != 0) throw std::runtime_error("GridEncoding: n_features=" + std::to_string(n_features) + " must be a multiple of N_FEATURES_PER_LEVEL=" + std::to_string(F));
+
+	GridMeta& g = e.grid;
+	g.n_dims = n_dims;
+	g.n_levels = n_levels;
+	g.n_feat = F;
+	g.grid_type = (uint32_t)grid_type;
+	g.interp = (uint32_t)interp;
+	g.max_level = 1.0f;
+	g.stochastic = enc.value("stochastic_interpolation", false) ? 1u : 0u;  // grid.h:1752
+	// grid.h:699-727; the scale / resolution table is computed here once (fp32, same expressions as
+	// common_device.h:886-895) and handed to the kernels, see GridMeta.
+	const float log2_per_level_scale = std::log2(per_level_scale);
+	uint32_t offset = 0;
+	for (uint32_t i = 0; i < n_levels; ++i) {
+		const float scale = exp2f((float)i * log2_per_level_scale) * (float)base_resolution - 1.0f;
+		const uint32_t resolution = (uint32_t)ceilf(scale) + 1;
+		g.scale[i] = scale;
+		g.resolution[i] = resolution;
+		const uint32_t max_params = std::numeric_limits<uint32_t>::max() / 2;
+		uint32_t params_in_level = std::pow((float)resolution, (float)n_dims) > (float)max_params ? max_params : powi(resolution, n_dims);
+		params_in_level = next_multiple(params_in_level, 8u);
+		if (grid_type == GridType::Tiled) {
+			params_in_level = std::min(params_in_level, powi(base_resolution, n_dims));
+		} else if (grid_type == GridType::Hash) {
+			params_in_level = std::min(params_in_level, 1u << log2_hashmap_size);
+		}
+		g.offset[i] = offset;
+		offset += params_in_level;
+		log_message(TCNN_LOG_DEBUG, "GridEncoding at level " + std::to_string(i) + ": resolution=" + std::to_string(resolution) +
+		                                " params_in_level=" + std::to_string(params_in_level));
+	}
+	g.offset[n_levels] = offset;
+	e.n_params = offset * F;
+	e.n_output_dims = n_features;
+	e.padded_output_width = n_features;
+	e.log2_hashmap_size = log2_hashmap_size;
+	e.base_resolution = base_resolution;
+	e.per_level_scale = per_level_scale;
+	return e;
+}
+
+EncodingDesc create_encoding_desc(uint32_t n_dims, const Json& enc, uint32_t alignment) {  // encoding.cu:131-145
+	const std::string name = enc.value("otype", "OneBlob");
+	EncodingDesc e;
+	if (equals_case_insensitive(name, "Grid") || equals_case_insensitive(name, "HashGrid") || equals_case_insensitive(name, "DenseGrid") ||
+	    equals_case_insensitive(name, "TiledGrid")) {
+		e = create_grid_encoding(n_dims, enc);
+	} else if (equals_case_insensitive(name, "Identity")) {
+		e.is_grid = false;
+		e.n_dims = n_dims;
+		e.id_scale = enc.value("scale", 1.0f);
+		e.id_offset = enc.value("offset", 0.0f);
+		e.n_output_dims = n_dims;
+		e.padded_output_width = n_dims;
+	} else if (equals_case_insensitive(name, "Frequency")) {  // encoding.cu:65-67
+		e.is_frequency = true;
+		e.n_dims = n_dims;
+		e.n_frequencies = enc.value("n_frequencies", 12u);
+		if (e.n_frequencies == 0 || e.n_frequencies > 32) throw std::runtime_error("FrequencyEncoding: n_frequencies must be in [1, 32]");
+		e.n_output_dims = n_dims * e.n_frequencies * 2u;
+		e.padded_output_width = e.n_output_dims;
+	} else if (equals_case_insensitive(name, "OneBlob")) {  // encoding.cu:118-120
+		e.is_oneblob = true;
+		e.n_dims = n_dims;
+		e.n_bins = enc.value("n_bins", 16u);
+		if (e.n_bins == 0 || (e.n_bins & (e.n_bins - 1)) != 0) throw std::runtime_error("Number of bins must be a power of 2");  // oneblob.h:174-176
+		e.n_output_dims = n_dims * e.n_bins;
+		e.padded_output_width = e.n_output_dims;
+	} else {
+		throw std::runtime_error("Encoding '" + name + "' not found (this build provides Grid/HashGrid/DenseGrid/TiledGrid, Frequency, OneBlob and Identity)");
+	}
+	if (alignment > 0) e.set_alignment(alignment);
+	return e;
+}
+
+Json NetworkDesc::hyperparams() const {
+	Json j = Json::object();
+	j["otype"] = "FullyFusedMLP";
+	j["activation"] = to_string((Activation)mlp.activation);
+	j["output_activation"] = to_string((Activation)mlp.output_activation);
+	j["n_neurons"] = mlp.width;
+	j["n_hidden_layers"] = n_hidden_layers;
+	return j;
+}
+
+static NetworkDesc create_network_desc(uint32_t n_input_dims, uint32_t n_output_dims, const Json& net) {  // network.cu:51-138
+	const std::string otype = net.value("otype", "MLP");
+	const bool known = equals_case_insensitive(otype, "MegakernelMLP") || equals_case_insensitive(otype, "FullyFusedMLP") ||
+	                   equals_case_insensitive(otype, "MLP") || equals_case_insensitive(otype, "CutlassMLP");
+	if (!known) throw std::runtime_error("Invalid network type: " + otype);
+	NetworkDesc d;
+	d.otype = otype;
+	const uint32_t n_neurons = net.value("n_neurons", 128u);
+	if (n_neurons != 16 && n_neurons != 32 && n_neurons != 64 && n_neurons != 128) {
+		throw std::runtime_error("FullyFusedMLP only supports 16, 32, 64, and 128 neurons, but got " + std::to_string(n_neurons) +
+		                         ". (CutlassMLP's arbitrary widths are not part of this build.)");
+	}
+	d.n_hidden_layers = net.value("n_hidden_layers", 5u);
+	if (d.n_hidden_layers == 0) throw std::runtime_error("FullyFusedMLP requires at least 1 hidden layer (3 layers in total).");
+	const Activation act = string_to_activation(net.value("activation", "ReLU"));
+	const Activation out_act = string_to_activation(net.value("output_activation", "None"));
+	d.n_output_dims = n_output_dims;
+	d.mlp.in_width = n_input_dims;
+	d.mlp.width = n_neurons;
+	d.mlp.padded_out = next_multiple(n_output_dims, 16u);  // fully_fused_mlp.cu:656
+	d.mlp.n_hidden_matmuls = d.n_hidden_layers - 1;
+	d.mlp.activation = (uint32_t)act;
+	d.mlp.output_activation = (uint32_t)out_act;
+	if (d.mlp.padded_out > MLP_MAX_OUT_WIDTH) {
+		throw std::runtime_error("FullyFusedMLP: more than " + std::to_string(MLP_MAX_OUT_WIDTH) + " output dimensions are not supported by this build.");
+	}
+	if (n_input_dims % 16 != 0 || n_input_dims > MLP_MAX_IN_WIDTH) {
+		throw std::runtime_error("FullyFusedMLP: input width " + std::to_string(n_input_dims) + " must be a multiple of 16 and at most " + std::to_string(MLP_MAX_IN_WIDTH));
+	}
+	return d;
+}
+
+void Model::finish() {
+	Json j = Json::object();
+	if (has_network) {
+		j["otype"] = "NetworkWithInputEncoding";
+		j["encoding"] = enc.hyperparams();
+		j["network"] = net.hyperparams();
+		hyper_json = j.dump();
+	} else {
+		hyper_json = enc.hyperparams().dump();
+	}
+}
+
+void Model::initialize_params(hipStream_t stream, Pcg32& rng, float* params_full_precision, float scale) const {
+	if (has_network) {
+		std::vector<float> host(n_mlp_params());
+		float* p = host.data();
+		auto xavier = [&](uint32_t rows, uint32_t cols) {  // gpu_matrix.h:292-307
+			const float s = scale * std::sqrt(6.0f / (float)(rows + cols));
+			for (size_t i = 0; i < (size_t)rows * cols; ++i) {
+				float t = rng.next_float() * 2.0f;
+				t = t * s;
+				p[i] = t - s;
+			}
+			p += (size_t)rows * cols;
+		};
+		xavier(net.mlp.width, net.mlp.in_width);
+		for (uint32_t i = 0; i < net.mlp.n_hidden_matmuls; ++i) xavier(net.mlp.width, net.mlp.width);
+		xavier(net.mlp.padded_out, net.mlp.width);
+		HIP_CHECK(hipMemcpyAsync(params_full_precision, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+		HIP_CHECK(hipStreamSynchronize(stream));
+	}
+	if (enc.n_params > 0) {
+		generate_random_uniform(stream, rng, enc.n_params, params_full_precision + n_mlp_params(), -1e-4f * scale, 1e-4f * scale);
+	}
+}
+
+Model make_nwie(uint32_t n_input_dims, uint32_t n_output_dims, const Json& encoding, const Json& network) {
+	Model md;
+	md.n_input_dims = n_input_dims;
+	md.enc = create_encoding_desc(n_input_dims, encoding, /*minimum_alignment(network)=*/16);  // network.cu:79-98 -> 16
+	md.has_network = true;
+	md.net = create_network_desc(md.enc.padded_output_width, n_output_dims, network);
+	md.finish();
+	return md;
+}
+
+static const char* const LOSS_NAMES[N_LOSS_TYPES] = {"L2",   "RelativeL2",   "L1",       "RelativeL1",         "Mape",
+                                                    "Smape", "CrossEntropy", "Variance", "RelativeL2Luminance"};  // loss.cu:57-65
+const char* loss_name(LossType loss) { return LOSS_NAMES[(int)loss]; }
+LossType string_to_loss(const std::string& s) {
+	for (int i = 0; i < N_LOSS_TYPES; ++i) {
+		if (equals_case_insensitive(s, LOSS_NAMES[i])) return (LossType)i;
+	}
+	throw std::runtime_error("Loss '" + s + "' not found");  // loss.cu:86
+}
+
+void parse_adam(AdamHyper& h, const Json& p) {
+	h.beta1 = p.value("beta1", h.beta1);
+	h.beta2 = p.value("beta2", h.beta2);
+	h.epsilon = p.value("epsilon", h.epsilon);
+	h.learning_rate = p.value("learning_rate", h.learning_rate);
+	h.l2_reg = p.value("l2_reg", h.l2_reg);
+	h.adabound = p.value("adabound", h.adabound);
+	h.relative_weight_decay = p.value("relative_decay", h.relative_weight_decay);
+	h.absolute_weight_decay = p.value("absolute_decay", h.absolute_weight_decay);
+	h.weight_clipping_magnitude = p.value("clipping_magnitude", h.weight_clipping_magnitude);
+	h.gradient_clipping_magnitude = p.value("gradient_clipping_magnitude", h.gradient_clipping_magnitude);
+	h.non_matrix_learning_rate_factor = p.value("non_matrix_learning_rate_factor", h.non_matrix_learning_rate_factor);
+	h.non_matrix_l2_reg = p.value("non_matrix_l2_reg", h.non_matrix_l2_reg);
+	h.optimize_matrix_params = p.value("optimize_matrix_params", h.optimize_matrix_params);
+	h.optimize_non_matrix_params = p.value("optimize_non_matrix_params", h.optimize_non_matrix_params);
+	h.skip_zero_grad_non_matrix_params = p.value("skip_zero_grad_non_matrix_params", h.skip_zero_grad_non_matrix_params);
+}
+
+}  // namespace tcnn_hip

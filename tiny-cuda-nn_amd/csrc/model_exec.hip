@@ -1,0 +1,358 @@
+// model_exec.hip -- the forward / backward / inference passes declared in model_exec.h (host code: scratch blocks, launch order, flags).
+#include "model_exec.h"
+
+#include <algorithm>
+#include <vector>
+
+#include "host_common.h"
+#include "switches.h"
+
+namespace tcnn_hip {
+
+void check_batch(uint32_t n, uint32_t widest) {
+	if (n % BATCH_SIZE_GRANULARITY != 0) {  // object.h:170, 217, 298
+		throw std::runtime_error("Batch size " + std::to_string(n) + " must be a multiple of " + std::to_string(BATCH_SIZE_GRANULARITY) + ".");
+	}
+	// the element-wise kernels index (sample, feature) pairs with 32 bits
+	if ((uint64_t)n * widest > 0xFFFFFFFFull) {
+		throw std::runtime_error("Batch size " + std::to_string(n) + " x " + std::to_string(widest) + " features exceeds 2^32 elements; split the batch.");
+	}
+}
+// The encodings without parameters (frequency / one-blob / identity), T = the 16-bit type or float: `out` and `dL_dy` have element
+// (feature k, sample i) at [k * stride_k + i * stride_i]
+template <typename T>
+static void parameterless_forward(hipStream_t stream, const EncodingDesc& e, const IoLayout& layout, uint32_t n, const float* input, T* out, uint32_t stride_k, uint32_t stride_i) {
+	if (e.is_frequency) {
+		frequency_forward(stream, n, e.n_dims, e.n_frequencies, e.padded_output_width, input, layout.in_stride_i, layout.in_stride_d, out, stride_k, stride_i);
+	} else if (e.is_oneblob) {
+		oneblob_forward(stream, n, e.n_dims, e.n_bins, e.padded_output_width, input, layout.in_stride_i, layout.in_stride_d, out, stride_k, stride_i);
+	} else {
+		identity_forward(stream, n, e.n_dims, e.padded_output_width, e.id_scale, e.id_offset, input, layout.in_stride_i, layout.in_stride_d, out, stride_k, stride_i);
+	}
+}
+template <typename T>
+static void parameterless_backward(hipStream_t stream, const EncodingDesc& e, const IoLayout& layout, uint32_t n, const float* input, const T* dL_dy, uint32_t stride_k, uint32_t stride_i,
+                                   float* dL_dinput) {
+	if (e.is_frequency) {
+		frequency_backward(stream, n, e.n_dims, e.n_frequencies, dL_dy, stride_k, stride_i, input, layout.in_stride_i, layout.in_stride_d, dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
+	} else if (e.is_oneblob) {
+		oneblob_backward(stream, n, e.n_dims, e.n_bins, dL_dy, stride_k, stride_i, input, layout.in_stride_i, layout.in_stride_d, dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
+	} else {
+		identity_backward(stream, n, e.n_dims, e.id_scale, dL_dy, stride_k, stride_i, dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
+	}
+}
+
+// Encoding forward into a feature-major (SoA) or sample-major (AoS) half matrix.
+void encoding_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const half_t* enc_params, half_t* out,
+                             bool soa, float* dy_dx) {
+	const EncodingDesc& e = md.enc;
+	const uint32_t stride_k = soa ? n : 1u, stride_i = soa ? 1u : e.padded_output_width;
+	ProfScope prof(profiler, stream, STAGE_GRID_FWD);
+	if (e.is_grid) {
+		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
+		grid_forward(stream, e.grid, io, enc_params, out, dy_dx);
+		const uint32_t n_to_pad = e.padded_output_width - e.n_output_dims;
+		if (n_to_pad > 0) {  // grid.h:757-766: padded dims are zero
+			if (soa) {
+				HIP_CHECK(hipMemsetAsync(out + (size_t)e.n_output_dims * n, 0, (size_t)n_to_pad * n * sizeof(half_t), stream));
+			} else {
+				HIP_CHECK(hipMemset2DAsync(out + e.n_output_dims, (size_t)e.padded_output_width * sizeof(half_t), 0, (size_t)n_to_pad * sizeof(half_t), n, stream));
+			}
+		}
+	} else {
+		parameterless_forward(stream, e, layout, n, input, out, stride_k, stride_i);
+	}
+}
+
+static bool backward_recomputes(const Model& md) { return g_fused_network_passes.load() != 0 && md.has_network && mlp_train_supported(md.net.mlp); }
+
+// NetworkWithInputEncoding::forward_impl / inference_mixed_precision_impl (:60-81).  ctx == nullptr: inference.
+void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, half_t* output, const half_t* params,
+                          ForwardCtx* ctx, bool prepare_input_gradients, const MlpF32Output* f32) {
+	check_batch(n, widest_matrix(md));
+	if (n == 0) return;
+	if (ctx) {
+		ctx->stream = stream;
+		ctx->n = n;
+	}
+	float* dy_dx = nullptr;
+	if (ctx && prepare_input_gradients && md.enc.is_grid) {
+		ctx->dy_dx = Scratch(stream, (size_t)md.enc.n_output_dims * n * md.n_input_dims * sizeof(float));
+		dy_dx = ctx->dy_dx.as<float>();
+	}
+	if (!md.has_network) {
+		encoding_forward(stream, profiler, md, layout, n, input, params, output, /*soa=*/false, dy_dx);
+		return;
+	}
+	// inference into the caller's fp32 matrix with an Identity encoding that pads nothing: the inference kernel reads the fp32 input itself
+	// (MlpF32Input; no encoding kernel, no encoded matrix)
+	const EncodingDesc& e = md.enc;
+	if (!ctx && !e.is_grid && !e.is_frequency && !e.is_oneblob && e.n_dims == e.padded_output_width && layout.in_stride_i == e.n_dims && layout.in_stride_d == 1u &&
+	    ((uintptr_t)input & 15u) == 0u && g_fused_identity_input.load() != 0 && mlp_infer_f32_input_supported(md.net.mlp, n)) {
+		MlpF32Input f32_input;
+		f32_input.x = input;
+		f32_input.scale = e.id_scale;
+		f32_input.offset = e.id_offset;
+		ProfScope prof(profiler, stream, STAGE_MLP_FWD);
+		// into the caller's fp32 matrix (network->inference) or into the padded 16-bit matrix (a module's inference, cpp_api.h:97)
+		mlp_infer_wave(stream, md.net.mlp, n, params, nullptr, f32 ? nullptr : output, f32 ? *f32 : MlpF32Output(), &f32_input);
+		return;
+	}
+	Scratch enc_local;
+	Scratch& enc = ctx ? ctx->enc : enc_local;
+	enc = Scratch(stream, (size_t)md.enc.padded_output_width * n * sizeof(half_t));
+	encoding_forward(stream, profiler, md, layout, n, input, params + md.n_mlp_params(), enc.as<half_t>(), /*soa=*/true, dy_dx);
+	half_t* hidden = nullptr;
+	if (ctx && !backward_recomputes(md)) {
+		ctx->hidden = Scratch(stream, (size_t)md.net.n_hidden_layers * n * md.net.mlp.width * sizeof(half_t));
+		hidden = ctx->hidden.as<half_t>();
+	}
+	ProfScope prof(profiler, stream, STAGE_MLP_FWD);
+	if (f32) {  // (inference_to_f32 below checked that the register-resident inference kernel takes this network)
+		mlp_infer_wave(stream, md.net.mlp, n, params, enc.as<half_t>(), nullptr, *f32);
+		return;
+	}
+	mlp_forward(stream, md.net.mlp, n, params, enc.as<half_t>(), hidden, output);
+}
+
+// network->inference into the caller's fp32 matrix (object.h:214-271).  Where the register-resident inference kernel runs the network it
+// writes the fp32 elements itself; otherwise the padded 16-bit result goes through trim_and_cast as in the reference.
+void inference_to_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const half_t* params, float* out, uint32_t stride_i, uint32_t stride_j) {
+	const uint32_t padded = md.padded_output_width(), width = md.output_width();
+	if (md.has_network && n > 0 && mlp_infer_wave_supported(md.net.mlp, n)) {
+		const MlpF32Output f32 = {out, width, stride_i, stride_j};
+		model_forward(stream, nullptr, md, layout, n, input, nullptr, params, nullptr, false, &f32);
+		return;
+	}
+	Scratch tmp(stream, (size_t)padded * n * sizeof(half_t));  // object.h:260
+	model_forward(stream, nullptr, md, layout, n, input, tmp.as<half_t>(), params, nullptr, false);
+	trim_and_cast(stream, n, padded, width, tmp.as<half_t>(), out, stride_i, stride_j);  // object.h:269-270
+}
+
+uint32_t widest_matrix(const Model& md) {
+	uint32_t w = std::max(md.enc.padded_output_width, md.n_input_dims);
+	if (md.has_network) w = std::max(w, std::max(md.net.mlp.width * md.net.n_hidden_layers, md.net.mlp.padded_out));
+	if (md.enc.is_grid) w = std::max(w, md.enc.n_output_dims * md.n_input_dims);  // dy_dx
+	return w;
+}
+
+// NetworkWithInputEncoding::backward_impl (:83-113) / GridEncodingTemplated::backward_impl (grid.h:817-908)
+void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const half_t* dL_doutput,
+                           half_t* dL_dparams, const float* input, const half_t* output, const half_t* params, int gradient_mode,
+                           uint32_t lds_level_budget) {
+	check_batch(n, widest_matrix(md));
+	if (n == 0) return;
+	if (ctx.n != n) throw std::runtime_error("backward: batch size does not match the forward context");
+	const bool recompute = md.has_network && !ctx.hidden.ptr;  // the context holds the encoded input only (see g_fused_network_passes)
+	if (recompute && (!ctx.enc.ptr || !mlp_train_supported(md.net.mlp))) {
+		throw std::runtime_error("backward: this context holds no saved activations and the network has no single-kernel backward pass");
+	}
+	const bool want_grads = gradient_mode != TCNN_GRADIENT_IGNORE && dL_dparams != nullptr;
+	const bool accumulate = gradient_mode == TCNN_GRADIENT_ACCUMULATE;
+	const EncodingDesc& e = md.enc;
+	if (!want_grads && !dL_dinput) return;
+
+	const half_t* dL_denc = dL_doutput;  // bare encoding: gradient of the encoding output, sample-major
+	uint32_t stride_k = 1u, stride_i = e.padded_output_width;
+	Scratch denc;
+	if (md.has_network) {
+		const bool need_denc = (want_grads && e.n_params > 0) || dL_dinput;
+		ProfScope prof(profiler, stream, STAGE_MLP_BWD);
+		Scratch params_t(stream, md.n_mlp_params() * sizeof(half_t));
+		mlp_transpose_weights(stream, md.net.mlp, params, params_t.as<half_t>());
+		const uint32_t n_partials = recompute ? mlp_train_n_partials(md.net.mlp, n, LossType::L2) : mlp_backward_n_partials(md.net.mlp, n);
+		Scratch partials;
+		if (want_grads) partials = Scratch(stream, (size_t)n_partials * md.n_mlp_params() * sizeof(float));
+		if (need_denc) denc = Scratch(stream, (size_t)e.padded_output_width * n * sizeof(half_t));
+		if (recompute) {  // forward from the encoded input again, then backward from the caller's dL/doutput, in one kernel
+			MlpLossArgs la = {LossType::L2, nullptr, nullptr, md.output_width(), 1.0f, 1u};
+			la.external_dL_doutput = dL_doutput;
+			const SlabOrder order = mlp_train(stream, md.net.mlp, n, params, params_t.as<half_t>(), ctx.enc.as<half_t>(), la, nullptr, nullptr,
+			                                  need_denc ? denc.as<half_t>() : nullptr, want_grads ? partials.as<float>() : nullptr, nullptr);
+			if (want_grads) mlp_finalize_gradients(stream, md.net.mlp, n_partials, partials.as<float>(), dL_dparams, accumulate, order);
+			if (!need_denc) return;
+			dL_denc = denc.as<half_t>();
+			stride_k = n;
+			stride_i = 1u;
+			encoding_backward(stream, profiler, md, layout, ctx, n, dL_dinput, dL_denc, stride_k, stride_i, dL_dparams, want_grads, accumulate, input, lds_level_budget);
+			return;
+		}
+		Scratch dpre;  // output activation: continue from dL/d(pre-activation) (fully_fused_mlp.cu:760-763)
+		if (md.net.mlp.output_activation != (uint32_t)Activation::None) {
+			if (!output) throw std::runtime_error("backward: the network output is required when an output activation is set");
+			dpre = Scratch(stream, (size_t)md.padded_output_width() * n * sizeof(half_t));
+			mlp_output_activation_backward(stream, md.net.mlp, n, output, dL_doutput, dpre.as<half_t>());
+			dL_doutput = dpre.as<half_t>();
+		}
+		Scratch deep;
+		if (const size_t deep_bytes = mlp_backward_workspace_bytes(md.net.mlp, n)) deep = Scratch(stream, deep_bytes);
+		mlp_backward(stream, md.net.mlp, n, params_t.as<half_t>(), ctx.enc.as<half_t>(), ctx.hidden.as<half_t>(), dL_doutput,
+		             need_denc ? denc.as<half_t>() : nullptr, want_grads ? partials.as<float>() : nullptr, deep.ptr);
+		if (want_grads) mlp_finalize_gradients(stream, md.net.mlp, n_partials, partials.as<float>(), dL_dparams, accumulate);
+		if (!need_denc) return;
+		dL_denc = denc.as<half_t>();
+		stride_k = n;
+		stride_i = 1u;
+	}
+
+	encoding_backward(stream, profiler, md, layout, ctx, n, dL_dinput, dL_denc, stride_k, stride_i, dL_dparams, want_grads, accumulate, input, lds_level_budget);
+}
+
+// the encoding's share of the backward pass: dL_denc has element (feature k, sample i) at [k * stride_k + i * stride_i]
+// grid_backward reports its kernels one by one (GridBackwardWorkspace::phase_hook); user = the pass's PhaseTimer
+struct PhaseTimer {
+	Profiler* profiler;
+	hipStream_t stream;
+	bool counts;  // false while the level groups after the first are launched: their time adds to the stage, the launch count of the step does not
+	hipEvent_t a = nullptr;  // the open phase's first event
+};
+static void grid_backward_phase_hook(void* user, int phase, int begin) {
+	PhaseTimer& t = *(PhaseTimer*)user;
+	Profiler* p = t.profiler;
+	const int stage = phase == 0 ? STAGE_GRID_BWD_SCATTER : STAGE_GRID_BWD;
+	if (!p || (p->only_stage >= 0 && p->only_stage != stage)) return;
+	if (begin) {
+		t.a = p->get();
+		HIP_CHECK(hipEventRecord(t.a, t.stream));
+	} else if (t.a) {
+		hipEvent_t b = p->get();
+		HIP_CHECK(hipEventRecord(b, t.stream));
+		p->spans.push_back({stage, t.a, b, t.counts});
+		t.a = nullptr;
+	}
+}
+
+// levels [a, b) of a grid as a grid of their own: the kernels index dL_dy and the gradients from the first of them
+static GridMeta grid_levels(const GridMeta& g, uint32_t a, uint32_t b) {
+	GridMeta s = g;
+	s.n_levels = b - a;
+	for (uint32_t l = 0; l <= b - a; ++l) s.offset[l] = g.offset[a + l] - g.offset[a];
+	for (uint32_t l = 0; l < b - a; ++l) {
+		s.scale[l] = g.scale[a + l];
+		s.resolution[l] = g.resolution[a + l];
+	}
+	return s;
+}
+
+// consecutive levels in `n_groups` groups, cut where the running parameter count passes k / n_groups of the total
+static std::vector<std::pair<uint32_t, uint32_t>> split_levels(const GridMeta& g, uint32_t n_groups) {
+	const uint32_t L = g.n_levels;
+	std::vector<std::pair<uint32_t, uint32_t>> level_ranges;
+	for (uint32_t k = 1, a = 0; k <= n_groups && a < L; ++k) {
+		uint32_t b = a + 1;
+		const uint64_t target = (uint64_t)g.offset[L] * k / n_groups;
+		while (b < L && (k == n_groups || g.offset[b] < target)) ++b;
+		if (k == n_groups) b = L;
+		level_ranges.push_back({a, b});
+		a = b;
+	}
+	return level_ranges;
+}
+
+void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const half_t* dL_denc,
+                              uint32_t stride_k, uint32_t stride_i, half_t* dL_dparams, bool want_grads, bool accumulate, const float* input,
+                              uint32_t lds_level_budget, const LevelGroups* groups) {
+	const EncodingDesc& e = md.enc;
+	if (e.is_grid) {
+		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
+		if (want_grads && e.n_params > 0) {
+			half_t* grid_grads = dL_dparams + md.n_mlp_params();
+			// Overwrite vs Accumulate (grid.h:865-867) is handled inside: the owner-computes kernel stores
+			// whole slices, so the reference's full-table memset is only issued for the atomic A/B mode.
+			const GridBackwardMode mode = (GridBackwardMode)g_grid_backward_mode.load();
+			if (lds_level_budget == 0) lds_level_budget = g_default_lds_slice_bytes;
+			// level groups: only where a level's treatment does not depend on its index among ALL levels (every level switched on,
+			// no per-level random stream) and nothing else rides on the pass
+			const uint32_t L = e.grid.n_levels, F = e.grid.n_feat;
+			uint32_t n_groups = groups ? std::min(std::max(groups->n_groups, 1u), L) : 1u;
+			if (e.grid.max_level < 1.0f || e.grid.stochastic != 0u) n_groups = 1;
+			const std::vector<std::pair<uint32_t, uint32_t>> level_ranges = split_levels(e.grid, n_groups);
+			// one workspace for all groups: the largest any of them asks for (a group of later levels can bucket levels that the plan of
+			// the whole grid, which takes the first MAX_BUCKET_LEVELS eligible ones, left to the other kinds)
+			GridBackwardWorkspace ws = grid_backward_workspace_size(e.grid, n, mode, lds_level_budget);
+			if (level_ranges.size() > 1) {
+				ws = GridBackwardWorkspace();
+				for (const auto& r : level_ranges) {
+					const GridBackwardWorkspace w = grid_backward_workspace_size(grid_levels(e.grid, r.first, r.second), n, mode, lds_level_budget);
+					ws.scratch_bytes = std::max(ws.scratch_bytes, w.scratch_bytes);
+					ws.n_counters = std::max(ws.n_counters, w.n_counters);
+				}
+			}
+			Scratch queues;
+			if (ws.scratch_bytes) {
+				queues = Scratch(stream, ws.scratch_bytes);
+				ws.scratch = queues.ptr;
+				ws.scratch_bytes = queues.bytes;
+				ws.counters = ZeroedCounters::get(stream, ws.n_counters);
+			}
+			PhaseTimer timer = {profiler, stream, /*counts=*/true};
+			ws.phase_hook = grid_backward_phase_hook;  // per-kernel timing when a profiler is attached
+			ws.hook_user = &timer;
+			if (level_ranges.size() <= 1) {
+				grid_backward(stream, e.grid, io, dL_denc, grid_grads, accumulate, mode, lds_level_budget, ws);
+				if (groups && groups->ready) groups->ready(groups->ctx, md.n_mlp_params(), md.n_mlp_params() + (size_t)e.grid.offset[L] * F);
+			} else {
+				for (const auto& r : level_ranges) {
+					const uint32_t a = r.first, b = r.second;
+					const GridMeta sub = grid_levels(e.grid, a, b);
+					timer.counts = a == 0;  // one backward pass per step, however many launches it takes
+					grid_backward(stream, sub, io, dL_denc + (size_t)a * F * stride_k, grid_grads + (size_t)e.grid.offset[a] * F, accumulate, mode, lds_level_budget, ws);
+					if (groups->ready) groups->ready(groups->ctx, md.n_mlp_params() + (size_t)e.grid.offset[a] * F, md.n_mlp_params() + (size_t)e.grid.offset[b] * F);
+				}
+			}
+		}
+		if (dL_dinput) {
+			if (!ctx.dy_dx.ptr) throw std::runtime_error("backward: dL_dinput requested but forward was not run with prepare_input_gradients");
+			grid_backward_input(stream, md.n_input_dims, e.n_output_dims, io, dL_denc, ctx.dy_dx.as<float>(), dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
+		}
+	} else if (dL_dinput) {
+		parameterless_backward(stream, e, layout, n, input, dL_denc, stride_k, stride_i, dL_dinput);
+	}
+}
+
+// ---- Encoding<float> (create_encoding(..., Precision::Fp32), cpp_api.cu:165-168): a bare encoding whose parameters, output and gradients are
+// fp32 and which COMPUTES in fp32, as the reference's instantiation does.  Output sample-major [n][padded] (cpp_api.cu:94-95).
+void encoding_forward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const float* params, float* out, ForwardCtx* ctx,
+                                 bool prepare_input_gradients) {
+	check_batch(n, widest_matrix(md));
+	if (n == 0) return;
+	const EncodingDesc& e = md.enc;
+	if (ctx) {
+		ctx->stream = stream;
+		ctx->n = n;
+	}
+	const uint32_t stride_k = 1u, stride_i = e.padded_output_width;
+	if (e.is_grid) {
+		float* dy_dx = nullptr;
+		if (ctx && prepare_input_gradients) {
+			ctx->dy_dx = Scratch(stream, (size_t)e.n_output_dims * n * md.n_input_dims * sizeof(float));
+			dy_dx = ctx->dy_dx.as<float>();
+		}
+		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
+		grid_forward_f32(stream, e.grid, io, params, out, dy_dx);
+		const uint32_t n_to_pad = e.padded_output_width - e.n_output_dims;
+		if (n_to_pad > 0) HIP_CHECK(hipMemset2DAsync(out + e.n_output_dims, (size_t)e.padded_output_width * sizeof(float), 0, (size_t)n_to_pad * sizeof(float), n, stream));
+	} else {
+		parameterless_forward(stream, e, layout, n, input, out, stride_k, stride_i);
+	}
+}
+void encoding_backward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const float* dL_doutput, float* dL_dparams,
+                                  const float* input) {
+	check_batch(n, widest_matrix(md));
+	if (n == 0) return;
+	if (ctx.n != n) throw std::runtime_error("backward: batch size does not match the forward context");
+	const EncodingDesc& e = md.enc;
+	const uint32_t stride_k = 1u, stride_i = e.padded_output_width;
+	if (e.is_grid) {
+		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
+		if (dL_dparams && e.n_params > 0) grid_backward_f32(stream, e.grid, io, dL_doutput, dL_dparams, /*accumulate=*/false);  // GradientMode::Overwrite, cpp_api.cu:115
+		if (dL_dinput) {
+			if (!ctx.dy_dx.ptr) throw std::runtime_error("backward: dL_dinput requested but forward was not run with prepare_input_gradients");
+			grid_backward_input_f32(stream, md.n_input_dims, e.n_output_dims, io, dL_doutput, ctx.dy_dx.as<float>(), dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
+		}
+	} else if (dL_dinput) {
+		parameterless_backward(stream, e, layout, n, input, dL_doutput, stride_k, stride_i, dL_dinput);
+	}
+}
+
+}  // namespace tcnn_hip
