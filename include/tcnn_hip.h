@@ -41,7 +41,11 @@ typedef void* tcnn_stream_t;                                /* hipStream_t (cuda
 /* cpp_api.h:72-75.  BF16 is this build's extension: libtcnn_hip_bf16.so is the same library compiled with bfloat16 as
  * the parameter / activation / gradient type (the reference picks its type at compile time too, TCNN_HALF_PRECISION);
  * its tcnn_preferred_precision() / param_precision() / output_precision() report TCNN_PRECISION_BF16 and every `void*`
- * below that is documented as fp16 carries bfloat16 instead.  Snapshots name the type ("__half" / "__nv_bfloat16"). */
+ * below that is documented as fp16 carries bfloat16 instead.  Snapshots name the type ("__half" / "__nv_bfloat16").
+ * Range of the bfloat16 grid-encoding parameter gradients: the backward pass sums an entry's contributions (dL/dy times an
+ * interpolation weight) in 64-bit fixed point with 2^-20 ... 2^-40 as its unit, chosen per level from the batch's own gradient
+ * magnitudes.  A contribution loses at most half a unit; one of magnitude 2^42 (4.4e12) or more may not fit 64 bits and is then
+ * DROPPED from the sum (the reference's atomics would carry it, or Inf): keep |dL/dy| of grid encodings below 2^42. */
 enum { TCNN_PRECISION_FP32 = 0, TCNN_PRECISION_FP16 = 1, TCNN_PRECISION_BF16 = 2 };
 enum { TCNN_LOG_INFO = 0, TCNN_LOG_DEBUG, TCNN_LOG_WARNING, TCNN_LOG_ERROR, TCNN_LOG_SUCCESS }; /* cpp_api.h:52-58 */
 enum { TCNN_GRADIENT_IGNORE = 0, TCNN_GRADIENT_OVERWRITE = 1, TCNN_GRADIENT_ACCUMULATE = 2 };  /* common.h:152-156 */

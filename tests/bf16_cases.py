@@ -242,3 +242,319 @@ def test_stress_shape_training_step_at_its_stated_size():
     s = steps.cpu().numpy().view(np.uint32)
     deficits = tm.optimizer_state()[3]
     assert np.array_equal((np.uint32(1) - s) if deficits else s, ref.steps)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Grid backward and second order across bfloat16's range, in the bucketed mode (the library's default, set explicitly).  Bars as in
+# tests/test_emu_bf16.py (helpers: tests/bf16_bars.py), per level from the plan rule the library documents (grid_kernels.hip,
+# make_backward_plan), restated here from the test's own sizes:
+#   * a slice is the largest power-of-two number of entries whose 64-bit-per-value table fits the default 128 KiB of LDS;
+#   * a level's samples are split into chunks only when a slice would see more than 65536 records (n * 2^D / slices):
+#     then ceil(records per slice / 32768) of them at most;
+#   * one owner per (slice, chunk) sums its records exactly in fixed point at the level's exponent k and rounds ONCE; the chunks
+#     of a slice meet in packed bfloat16 atomics (one rounding each); records that overflow their queue, beyond 2^18 of them per
+#     call, are added by global atomics (one rounding per record).
+#   |got - ref| <= c * 2^-9 * (absacc + floor) + floor, c = 2 per rounding, floor = N_e * 2^-(k+1).
+# ---------------------------------------------------------------------------------------------------------------------
+from bf16_bars import ONE_ROUNDING, TINY, absf, level_k, max_abs_per_level, record_counts, second_order_magnitudes, spread  # noqa: E402
+
+SLICE_BYTES = 128 * 1024
+
+
+class bucketed_mode:
+    """the bucketed backward with the given owner form, restored on the way out"""
+
+    def __init__(self, owner=0):
+        self.owner = owner
+
+    def __enter__(self):
+        C = tcnn()._C
+        self.saved = (C.get_grid_backward_mode(), C.get_grid_owner_mode())
+        C.set_grid_backward_mode(3)
+        C.set_grid_owner_mode(self.owner)
+
+    def __exit__(self, *exc):
+        C = tcnn()._C
+        C.set_grid_backward_mode(self.saved[0])
+        C.set_grid_owner_mode(self.saved[1])
+
+
+def plan_rule(og, n):
+    """(slices, most chunks) per level by the rule above"""
+    F = og.n_features_per_level
+    corners = 1 if og.interpolation == O.INTERP_NEAREST else 1 << og.n_dims
+    per_slice = 1
+    while 2 * per_slice * F * 8 <= SLICE_BYTES:
+        per_slice *= 2
+    slices, chunks = [], []
+    for l in range(og.n_levels):
+        entries = og.offsets[l + 1] - og.offsets[l]
+        nb = -(-entries // per_slice)
+        records = n * corners // nb
+        slices.append(nb)
+        chunks.append(1 if records <= 65536 else -(-records // 32768))
+    return np.array(slices), np.array(chunks)
+
+
+def bucketed_bar(og, pos, per_sample, absacc, roundings_per_level, atomics_per_record=False):
+    """(bar, floor).  k per level: the rule at the level's owners; where the chunk count is only bounded (1 ... most), the coarser k."""
+    slices, chunks = plan_rule(og, pos.shape[0])
+    counts = record_counts(og, pos)
+    ks = [min(level_k(per_sample[:, l], int(slices[l])), level_k(per_sample[:, l], int(slices[l] * chunks[l]))) for l in range(og.n_levels)]
+    floor = counts * spread(og, [2.0 ** -(k + 1) for k in ks])
+    c = spread(og, np.asarray(roundings_per_level, np.float64)) + (counts if atomics_per_record else 0.0)
+    return c * ONE_ROUNDING * (absacc + floor) + floor + TINY, floor, ks
+
+
+def slices_that_must_go_wide(og, n, absacc, ks):
+    """The packed owner (even F) keeps a slice only if the magnitudes of its records sum to less than 0.9375 * 2^(31-k) per feature
+    (OwnerScale::safe_abs_sum); otherwise it redoes the slice with 64 bits per value at the same k.  Counted from the oracle's
+    accumulated magnitudes: sole-owner slices whose sum for some feature is beyond 2^(31-k) -- clear of the bound's own rounding."""
+    F = og.n_features_per_level
+    if F % 2:
+        return 0
+    per_slice = 1
+    while 2 * per_slice * F * 8 <= SLICE_BYTES:
+        per_slice *= 2
+    slices, chunks = plan_rule(og, n)
+    count = 0
+    for l in range(og.n_levels):
+        if chunks[l] != 1:
+            continue
+        a = absacc[og.offsets[l] * F:og.offsets[l + 1] * F].reshape(-1, F)
+        for b in range(int(slices[l])):
+            count += bool((a[b * per_slice:(b + 1) * per_slice].sum(axis=0) > 2.0 ** (31 - ks[l])).any())
+    return count
+
+
+def bits_of(t):
+    return t.detach().contiguous().cpu().view(torch.int16).numpy().view(np.uint16).copy()
+
+
+GRID_TYPES = {"Dense": O.GRID_DENSE, "Tiled": O.GRID_TILED, "Hash": O.GRID_HASH}
+BACKWARD_SHAPES = [(2, "Dense", 1), (2, "Dense", 4), (4, "Dense", 8), (2, "Tiled", 8), (4, "Tiled", 4), (4, "Tiled", 1), (3, "Hash", 2)]
+
+
+@pytest.mark.parametrize("magnitude", [2.0 ** -100, 2.0 ** -40, 3e-3, 2.0, 300.0, 2.0 ** 12, 2.0 ** 20, "mixed"], ids=str)
+@pytest.mark.parametrize("d,gtype,F", BACKWARD_SHAPES)
+def test_grid_backward_across_the_range(d, gtype, F, magnitude):
+    """Dense, Tiled and hashed tables, F = 1, 4, 8, D = 2 ... 4: dL/dy ~ N(0, 1) times 2^-100 ... 2^20 and a mixed batch (1 % of the
+    samples at 2^10, the rest at 2^-20).  n * 2^D <= 65536: every slice has ONE owner, so c = 2 (one rounding) whatever N_e, the three
+    owner forms give the same BITS, and a zero is legitimate only where the exact fixed-point sum is zero: |ref| inside the floor."""
+    C = tcnn()._C
+    L = 5 if d == 2 else 3
+    enc = dict(otype="Grid", type=gtype, n_levels=L, n_features_per_level=F, log2_hashmap_size=14, base_resolution=4, per_level_scale=1.6)
+    m = C.create_encoding(d, enc)
+    og = O.grid_init(d, L, F, 14, 4, 1.6, GRID_TYPES[gtype], O.INTERP_LINEAR)
+    assert m.n_params() == og.n_params
+    n = 4096
+    assert n * (1 << d) <= 65536 and np.all(plan_rule(og, n)[1] == 1)
+    pos = positions(n, d, seed=7)
+    z = np.random.default_rng(2).standard_normal((n, L * F))
+    factor = np.where(np.arange(n) % 100 == 0, 2.0 ** 10, 2.0 ** -20)[:, None] if magnitude == "mixed" else magnitude
+    dy = np.zeros((n, m.n_output_dims()), np.uint16)
+    dy[:, :L * F] = O.f2h((z * factor).astype(np.float32))
+    params = O.f2h(O.generate_random_uniform(O.pcg32(9), og.n_params, -1.0, 1.0))
+    x, p = torch.from_numpy(pos).cuda(), h_t(params).requires_grad_(True)
+    ctx, out = m.fwd(x, p)
+    got, wide = [], []
+    for owner in (0, 1, 2):
+        with bucketed_mode(owner):
+            before = C.grid_owner_wide_slices()
+            _, grad = m.bwd(ctx, x, p, out, h_t(dy))
+            torch.cuda.synchronize()
+            wide.append(C.grid_owner_wide_slices() - before)
+        got.append(bits_of(grad))
+    assert np.array_equal(got[0], got[1]) and np.array_equal(got[0], got[2])
+    gotf = O.h2f(got[0]).astype(np.float64)
+    ref = O.grid_backward(og, pos, dy[:, :L * F])
+    absacc = O.grid_backward(og, pos, absf(dy[:, :L * F]))
+    bar, floor, ks = bucketed_bar(og, pos, max_abs_per_level(dy[:, :L * F], L, F), absacc, [1] * L)
+    err = np.abs(gotf - ref)
+    must = slices_that_must_go_wide(og, n, absacc, ks)
+    print("worst |err| / bar:", float((err / bar).max()), "k:", ks, "wide slices:", wide[0], "of which the bound demands:", must)
+    assert np.isfinite(gotf).all() and np.all(err <= bar)
+    assert not np.any((gotf == 0) & (np.abs(ref) > floor + TINY))
+    # the 64-bit redo at the level's own k really runs on the hardware where the bound says it must (2^12 and up, the mixed batch: k is at
+    # its coarsest and still the slices' sums pass 2^(31-k)) -- and gave the bits of the other two forms above
+    assert wide[0] >= must and (must > 0 or F % 2 or magnitude in (2.0 ** -100, 2.0 ** -40, 3e-3, 2.0))
+
+
+def test_grid_backward_accumulates():
+    """GradientMode::Accumulate in bfloat16 (mirrors test_gradient_modes_and_data_parallel_linearity): a second identical step on top of
+    the first.  n * 2^D <= 65536: every grid slice has one owner, which adds its exactly summed, once-rounded result -- the same bits as
+    the first step's -- to what is there: 2 x full, exact in any binary format.  The network's weight gradients are fp32 partial sums
+    rounded once and added to the old value: one rounding of 2 x full, and one of full should the partial sums be grouped differently."""
+    T = tcnn()
+    cfg = config_hash(log2_hashmap_size=15, per_level_scale=1.5)
+    tm = T.create_from_config(3, 4, cfg)
+    n = 4096
+    pos = positions(n, 3, seed=3)
+    tgt = targets_for(pos, 4)
+    x, t = torch.from_numpy(pos).cuda(), torch.from_numpy(tgt).cuda()
+    w = tm.params_full_precision.clone()
+    nm = tm.n_mlp_params
+    w[nm:] *= 1.0e3
+    tm.set_params_full_precision(w)
+    with bucketed_mode():
+        tm.training_step(x, t, run_optimizer=False, want_context=False)
+        full = tm.param_gradients.float().cpu().numpy().astype(np.float64)
+        tm.training_step(x, t, run_optimizer=False, gradient_mode=T._C.GradientMode.Accumulate, want_context=False)
+        twice = tm.param_gradients.float().cpu().numpy().astype(np.float64)
+    assert np.isfinite(twice).all() and np.abs(full[nm:]).max() > 0
+    assert np.array_equal(twice[nm:], 2 * full[nm:])
+    assert np.all(np.abs(twice[:nm] - 2 * full[:nm]) <= 3 * ONE_ROUNDING * np.abs(full[:nm]) + TINY)
+
+
+@pytest.mark.parametrize("clustered", [False, True])
+def test_bucketed_grid_backward_full_size(clustered):
+    """test_bucketed_grid_backward_full_size in bfloat16 (N = 2^18, T = 2^19).  Uniform inputs: nothing overflows beyond the inline
+    list, every (slice, chunk) owner is exact: c = 2 x (1 + chunks where a level is chunked), and the three owner forms agree bit for
+    bit on the levels with one owner per slice.  Clustered inputs (3/4 of the batch inside a 1 % cube): the slices under the cluster
+    that fail the packed owner's int32 bound are redone with 64 bits per value at the level's data-dependent k, queues overflow and their records go through global atomics -- one more rounding per record of the entry, at the worst."""
+    C = tcnn()._C
+    enc = dict(HASH_ENCODING)
+    m = C.create_encoding(3, enc)
+    og = O.grid_init(3, enc["n_levels"], enc["n_features_per_level"], enc["log2_hashmap_size"], enc["base_resolution"], enc["per_level_scale"])
+    L, F = og.n_levels, og.n_features_per_level
+    n = 1 << 18
+    pos = positions(n, 3, seed=21)
+    if clustered:
+        pos[n // 4:] = pos[:3 * n // 4] * 0.01 + 0.37
+    rng = np.random.default_rng(3)
+    dy = O.f2h((rng.standard_normal((n, m.n_output_dims())) * 0.02).astype(np.float32))
+    x = torch.from_numpy(pos).cuda()
+    p = torch.zeros(og.n_params, dtype=BF, device="cuda").requires_grad_(True)
+    ctx, y = m.fwd(x, p)
+    got = []
+    wide = []
+    for owner in (0, 1, 2):
+        with bucketed_mode(owner):
+            before = C.grid_owner_wide_slices()
+            _, dp = m.bwd(ctx, x, p, y, h_t(dy))
+            torch.cuda.synchronize()
+            wide.append(C.grid_owner_wide_slices() - before)
+        got.append(bits_of(dp))
+    slices, chunks = plan_rule(og, n)
+    ref = O.grid_backward(og, pos, dy[:, :L * F])
+    absacc = O.grid_backward(og, pos, absf(dy[:, :L * F]))
+    bar, floor, ks = bucketed_bar(og, pos, max_abs_per_level(dy[:, :L * F], L, F), absacc, [1 + (c if c > 1 else 0) for c in chunks], atomics_per_record=clustered)
+    # (the hash spreads the cluster's records over a level's whole table, and a queue holds no more than its capacity -- the rest of a
+    # clustered slice's records travel through the overflow list, past the owner's bound: the count of slices that must go wide is
+    # known for uniform inputs only; test_grid_backward_across_the_range is where the redo is certain to run)
+    if not clustered:
+        assert wide[0] >= slices_that_must_go_wide(og, n, absacc, ks)
+    for o in range(3):
+        gotf = O.h2f(got[o]).astype(np.float64)
+        err = np.abs(gotf - ref)
+        print("owner form", o, "worst |err| / bar:", float((err / bar).max()), "wide slices:", wide[o])
+        assert np.isfinite(gotf).all() and np.all(err <= bar)
+    if not clustered:
+        n_sole = 0
+        for l in range(L):
+            if chunks[l] == 1:
+                lo, hi = og.offsets[l] * F, og.offsets[l + 1] * F
+                assert np.array_equal(got[0][lo:hi], got[1][lo:hi]) and np.array_equal(got[0][lo:hi], got[2][lo:hi]), l
+                assert not np.any((O.h2f(got[0][lo:hi]) == 0) & (np.abs(ref[lo:hi]) > floor[lo:hi] + TINY)), l
+                n_sole += 1
+        assert n_sole >= 8
+
+
+@pytest.mark.parametrize("ddx_scale", [1.0, 1e-4])
+@pytest.mark.parametrize("interp", ["Linear", "Smoothstep"])
+def test_grid_second_order_with_small_and_unit_ddx(interp, ddx_scale):
+    """backward_backward_input in bfloat16 (mirrors test_grid_second_order_through_c_abi_and_double_backward of the fp16 suite) with
+    ddx ~ N(0, 1) and N(0, 1) * 1e-4 (eikonal-sized).  The level sum that picks the owners' exponent is taken from the records the
+    scatter emits (|dy| * sum over the corners of |weight|): with k from |dL/dy| alone the 1e-4 case lost every record below 2^-21.
+    One owner per slice (n * 2^D <= 65536); five roundings of magnitudes bounded by absacc (tests/test_emu_bf16.py
+    test_grid_second_order): c = 10.  A zero is legitimate where the kernel's exact sum is inside the floor: the oracle's then lies
+    within the floor and the four roundings that separate the two sides' records.  d(dL_dx)/d(dL_dy) bit-exact."""
+    C = tcnn()._C
+    enc = dict(HASH_ENCODING_SMALL, interpolation=interp)
+    d = 3
+    m = C.create_encoding(d, enc)
+    og = O.grid_init(d, enc["n_levels"], enc["n_features_per_level"], enc["log2_hashmap_size"], enc["base_resolution"], enc["per_level_scale"],
+                     O.GRID_HASH, O.INTERP_SMOOTHSTEP if interp == "Smoothstep" else O.INTERP_LINEAR)
+    n = 2048
+    assert np.all(plan_rule(og, n)[1] == 1)
+    pos = positions(n, d, seed=31)
+    rng = np.random.default_rng(5)
+    params = O.f2h((rng.random(og.n_params, dtype=np.float32) * 2 - 1) * 0.5)
+    K = m.n_output_dims()
+    dy = O.f2h(rng.standard_normal((n, K)).astype(np.float32))
+    ddx = (rng.standard_normal((n, d)) * ddx_scale).astype(np.float32)
+    x = torch.from_numpy(pos).cuda().requires_grad_(True)
+    p = h_t(params).requires_grad_(True)
+    ctx, y = m.fwd(x, p)
+    with bucketed_mode():
+        d_dy, d_p, d_x = m.bwd_bwd_input(ctx, x, p, torch.from_numpy(ddx).cuda(), h_t(dy).requires_grad_(True))
+        torch.cuda.synchronize()
+    KF = og.n_levels * og.n_features_per_level
+    _, dydx = O.grid_forward(og, params, pos, want_dy_dx=True)
+    gp_ref, dLddy_ref, dx_ref = O.grid_backward_backward_input(og, params, pos, ddx, dy[:, :KF], dy_dx=dydx)
+    assert np.array_equal(h_np(d_dy)[:, :KF], dLddy_ref[:, :KF])
+    assert np.allclose(d_x.cpu().numpy(), dx_ref, rtol=1e-3, atol=1e-4 * max(ddx_scale, np.abs(dx_ref).max()))
+    absacc, per_sample = second_order_magnitudes(og, pos, ddx, dy[:, :KF])
+    bar, floor, ks = bucketed_bar(og, pos, per_sample, absacc * (1 + 1e-5), [5] * og.n_levels)
+    got = d_p.float().cpu().numpy().astype(np.float64)
+    err = np.abs(got - gp_ref)
+    print("worst |err| / bar:", float((err / bar).max()))
+    assert np.isfinite(got).all() and np.all(err <= bar)
+    assert np.abs(gp_ref).max() > 0 and not np.any((got == 0) & (np.abs(gp_ref) > floor + 4 * ONE_ROUNDING * absacc + TINY))
+
+
+@pytest.mark.parametrize("act,out_act", [("LeakyReLU", "None"), ("Exponential", "Sigmoid"), ("Sigmoid", "Exponential"), ("Squareplus", "Tanh"),
+                                         ("Softplus", "Softplus"), ("Tanh", "Squareplus"), ("None", "ReLU")])
+def test_network_activations(act, out_act):
+    """test_network_activations of the fp16 suite in bfloat16, with this file's bars for the oracle comparisons (outputs RAE p99 < 3e-2,
+    gradients relative L2 < 2e-2 and, two hidden layers, RAE p99 < 3e-2).  Fused training kernel against forward() + backward(): the
+    fp16 suite's bars in units of the type's spacing, which is 8 x coarser here (rtol 4e-3 -> 3.2e-2, 2e-3 -> 1.6e-2, 2^-10 -> 2^-7)."""
+    C = tcnn()._C
+    IN, W, OUT, H = 32, 64, 4, 2
+    m = C.create_network(IN, OUT, dict(MLP_64x2, activation=act, output_activation=out_act))
+    om = O.mlp_init(IN, W, OUT, H, activation=O.ACTIVATION_NAMES.index(act), output_activation=O.ACTIVATION_NAMES.index(out_act))
+    hp = m.hyperparams()["network"]
+    assert hp["output_activation"] == out_act and hp["activation"] == act
+    ph = O.f2h(O.mlp_init_params(om, O.pcg32(3)) * 0.5)
+    n = 1024
+    rng = np.random.default_rng(13)
+    xin = rng.random((n, IN), dtype=np.float32) * 0.5
+    x = torch.from_numpy(xin).cuda().requires_grad_(True)
+    p = h_t(ph).requires_grad_(True)
+    ctx, y = m.fwd(x, p)
+    torch.cuda.synchronize()
+    enc = O.identity_forward(xin, IN)
+    hid_ref, out_ref = O.mlp_forward(om, ph, enc)
+    assert np.percentile(rae(O.h2f(h_np(y))[:, :OUT], O.h2f(out_ref)[:, :OUT]), 99) < 3e-2
+    dy = np.zeros((n, 16), np.float32)
+    dy[:, :OUT] = rng.standard_normal((n, OUT)).astype(np.float32) * 0.05
+    dyh = O.f2h(dy)
+    dx, dp = m.bwd(ctx, x, p, y, h_t(dyh))
+    torch.cuda.synchronize()
+    gref, dref = O.mlp_backward(om, ph, enc, hid_ref, out_ref, dyh)
+    gq = dp.float().cpu().numpy()
+    assert np.linalg.norm(gq - gref) < 2e-2 * np.linalg.norm(gref) and np.percentile(rae(gq, gref), 99) < 3e-2
+    dx_ref = O.h2f(dref)[:, :IN].astype(np.float64)
+    assert np.linalg.norm(dx.float().cpu().numpy() - dx_ref) < 2e-2 * np.linalg.norm(dx_ref)
+
+    T = tcnn()
+    cfg = config_hash(log2_hashmap_size=14)
+    cfg["network"] = dict(cfg["network"], activation=act, output_activation=out_act)
+    tm = T.create_from_config(3, 4, cfg, seed=3)
+    w = tm.params_full_precision.clone()
+    w[tm.n_mlp_params:] *= 1.0e3
+    tm.set_params_full_precision(w)
+    pos = positions(2048, 3, seed=4)
+    xx, tt = torch.from_numpy(pos).cuda(), torch.from_numpy(targets_for(pos, 4)).cuda()
+    ctx_f = tm.training_step(xx, tt, run_optimizer=False)
+    g_fused, loss_fused = tm.param_gradients.clone(), tm.loss(ctx_f)
+    c2 = tm.forward(xx, tt)
+    tm.backward(c2, xx)
+    g_pair, nm = tm.param_gradients, tm.n_mlp_params
+    grid_pair, grid_fused = g_pair[nm:].float(), g_fused[nm:].float()
+    assert (grid_pair != grid_fused).float().mean() < 0.02
+    assert torch.allclose(grid_pair, grid_fused, rtol=3.2e-2, atol=1.6e-2 * float(grid_fused.abs().max()))
+    assert (g_pair[:nm] != g_fused[:nm]).float().mean() < 0.05
+    assert torch.allclose(g_pair[:nm].float(), g_fused[:nm].float(), rtol=1.6e-2, atol=1e-3 * float(g_fused[:nm].float().abs().max()) * 2.0 ** -7 + 1e-7)
+    assert abs(tm.loss(c2) - loss_fused) <= 1e-5 * abs(loss_fused) + 1e-9
+    assert torch.isfinite(g_fused.float()).all()

@@ -12,19 +12,35 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 _CSRC = os.path.join(_ROOT, "tiny-cuda-nn_amd", "csrc")
-_LIB = os.path.join(_HERE, "libtcnn_emu.so")
+_LIB = os.path.join(_HERE, "libtcnn_emu.so")            # IEEE fp16, as libtcnn_hip.so
+_LIB_BF16 = os.path.join(_HERE, "libtcnn_emu_bf16.so")  # the same sources with -DTCNN_BF16, as libtcnn_hip_bf16.so
 _CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 
 
-def build(force=False):
+def _build_command(path, extra, force):
+    """The compiler command that (re)builds `path`, or None if it is newer than every source."""
     srcs = [os.path.join(_HERE, f) for f in ("emu_driver.cpp", "hip_emu.h")]
     srcs += [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".h"))]
     newest = max(os.path.getmtime(s) for s in srcs)
-    if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < newest:
-        subprocess.check_call([_CLANG, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-Wno-pass-failed",
-                               "-DTCNN_MLP_WAVE_BLOCKS=3",  # few workgroups: the persistent strip loop runs uneven shares
-                               "-I" + _HERE, "-I" + _CSRC, os.path.join(_HERE, "emu_driver.cpp"), "-o", _LIB])
+    if not force and os.path.exists(path) and os.path.getmtime(path) >= newest:
+        return None
+    # Both libraries define the same functions and the emulator keeps global state (::emu::g, an inline variable).  Everything is
+    # compiled with hidden visibility except the driver's extern "C" entry points, and linked with -Bsymbolic: neither library
+    # exports its state or can bind to the other's, so both can live in one process (ctypes loads them RTLD_LOCAL).
+    return [_CLANG, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
+            "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wl,-Bsymbolic",
+            "-Wno-pass-failed",
+            "-DTCNN_MLP_WAVE_BLOCKS=3",  # few workgroups: the persistent strip loop runs uneven shares
+            ] + extra + ["-I" + _HERE, "-I" + _CSRC, os.path.join(_HERE, "emu_driver.cpp"), "-o", path]
+
+
+def build(force=False):
+    """Builds both emulator libraries (side by side: each is one long translation unit); returns the fp16 one's path."""
+    commands = [c for c in (_build_command(_LIB, [], force), _build_command(_LIB_BF16, ["-DTCNN_BF16"], force)) if c]
+    running = [subprocess.Popen(c) for c in commands]
+    failed = [c for c, p in zip(commands, running) if p.wait() != 0]
+    if failed:
+        raise subprocess.CalledProcessError(1, failed[0])
     return _LIB
 
 
@@ -51,15 +67,23 @@ class EmuAdam(C.Structure):
                                        "skip_zero_grad_non_matrix_params")]
 
 
-_lib = None
+_libs = {}
+_bf16 = False
+
+
+def set_bf16(on):
+    """Selects the library the functions of this module call from here on: the bfloat16 build (True) or the fp16 one (False, the default).
+    Returns the previous choice.  A module that tests the bf16 build switches in a module-scoped fixture and restores on the way out."""
+    global _bf16
+    previous, _bf16 = _bf16, bool(on)
+    return previous
 
 
 def lib():
-    global _lib
-    if _lib is None:
+    if _bf16 not in _libs:
         build()
-        _lib = C.CDLL(_LIB)
-    return _lib
+        _libs[_bf16] = C.CDLL(_LIB_BF16 if _bf16 else _LIB)
+    return _libs[_bf16]
 
 
 def _p(a):
@@ -190,6 +214,47 @@ def grid_backward_backward(g, positions, ddx, dL_dy_soa_h, params_h, dy_dx_kn):
                                          _p(np.ascontiguousarray(dy_dx_kn, dtype=np.float32)), _p(grad), _p(dLddy), _p(dx))
     assert r == 0
     return grad, dLddy, dx
+
+
+PLAN_FIXED64, PLAN_FLOAT, PLAN_GLOBAL_ATOMIC, PLAN_BUCKET = 0, 1, 2, 3
+
+
+def grid_backward_plan(g, n, mode=BUCKETED, accumulate=False, lds_budget=0):
+    """The host plan of a backward call (make_backward_plan, host code of the library): per level (kind, table slices, sample chunks
+    per slice), kind one of PLAN_*.  Mode ATOMIC has no plan (every record is a global atomic)."""
+    out = np.zeros((g.og.n_levels, 3), dtype=np.uint32)
+    assert lib().emu_grid_backward_plan(C.byref(g.c), C.c_uint32(n), C.c_int(mode), C.c_int(int(accumulate)), C.c_uint32(lds_budget), _p(out)) == 0
+    return out
+
+
+def level_sum_units(total):
+    """level_sum_units() of grid_kernels.hip: a workgroup's fp32 total of clamped |record| -> 2^-32 units in 64 bits"""
+    fn = lib().emu_level_sum_units
+    fn.restype = C.c_uint64
+    return int(fn(C.c_float(total)))
+
+
+def saturating_add_u64(a, b):
+    fn = lib().emu_saturating_add_u64
+    fn.restype = C.c_uint64
+    return int(fn(C.c_uint64(a), C.c_uint64(b)))
+
+
+def atomic_add_h2(a_bits, b_bits):
+    """a + b through the emulator's packed 16-bit atomic add, on arrays of bit patterns"""
+    n = len(a_bits)
+    a = np.zeros(n + (n & 1), dtype=np.uint16)
+    b = np.zeros_like(a)
+    a[:n], b[:n] = a_bits, b_bits
+    lib().emu_atomic_add_h2(C.c_uint64(a.size), _p(a), _p(b))
+    return a[:n]
+
+
+def fma_h(a_bits, b_bits, c_bits):
+    a, b, c = (np.ascontiguousarray(v, dtype=np.uint16) for v in (a_bits, b_bits, c_bits))
+    out = np.zeros_like(a)
+    lib().emu_fma_h(C.c_uint64(a.size), _p(a), _p(b), _p(c), _p(out))
+    return out
 
 
 def grid_backward_input(g, dL_dy_soa_h, dy_dx):

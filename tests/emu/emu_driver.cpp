@@ -10,7 +10,20 @@
 
 using namespace tcnn_hip;
 
+// (the library is built with hidden visibility -- emu.py says why; only the entry points below are exported)
+#pragma GCC visibility push(default)
 extern "C" {
+
+// ---- probes of single device functions ------------------------------------------------------------------------
+unsigned long long emu_level_sum_units(float total) { return level_sum_units(total); }
+unsigned long long emu_saturating_add_u64(unsigned long long a, unsigned long long b) { return saturating_add_u64(a, b); }
+// a[i] += b[i] through the packed 16-bit atomic of the emulator (n even)
+void emu_atomic_add_h2(uint64_t n, uint16_t* a, const uint16_t* b) {
+	for (uint64_t i = 0; i + 1 < n; i += 2) atomic_add_h2((half_t*)a + i, *(const h2*)((const half_t*)b + i));
+}
+void emu_fma_h(uint64_t n, const uint16_t* a, const uint16_t* b, const uint16_t* c, uint16_t* out) {
+	for (uint64_t i = 0; i < n; ++i) ((half_t*)out)[i] = fma_h(((const half_t*)a)[i], ((const half_t*)b)[i], ((const half_t*)c)[i]);
+}
 
 struct EmuGrid {
 	uint32_t n_dims, n_levels, n_feat, grid_type, interp;
@@ -68,6 +81,26 @@ uint32_t emu_grid_forward_plan(const EmuGrid* e, uint32_t n, uint32_t tile_sampl
 		fprintf(stderr, "emu_grid_forward_plan: %s\n", ex.what());
 		return 0;
 	}
+}
+
+// The host plan of a backward call, per level: out[l] = {kind (SliceKind: 0 fixed-point slices, 1 fp32 / packed slices, 2 global atomics,
+// 3 bucketed), table slices, sample chunks per slice}.  mode / accumulate / lds_budget as grid_backward() takes them.
+int emu_grid_backward_plan(const EmuGrid* e, uint32_t n, int mode, int accumulate, uint32_t lds_budget, uint32_t* out) {
+	try {
+		const GridMeta meta = make_meta(e);
+		const bool packed = mode != (int)GridBackwardMode::SlicedF32, bucketed = mode == (int)GridBackwardMode::Bucketed;
+		const BackwardPlan bp = make_backward_plan(meta, n, packed, bucketed, accumulate != 0, lds_budget);
+		for (uint32_t p = 0; p < bp.slices.n_items; ++p) {
+			uint32_t* o = out + 3u * bp.slices.level[p];
+			o[0] = bp.slices.kind[p];
+			o[1] = bp.slices.n_slices[p];
+			o[2] = bp.n_chunks[p];
+		}
+	} catch (const std::exception& ex) {
+		fprintf(stderr, "emu_grid_backward_plan: %s\n", ex.what());
+		return 1;
+	}
+	return 0;
 }
 
 void emu_set_grid_owner_mode(int mode) { grid_owner_mode() = mode; }
@@ -385,10 +418,12 @@ int emu_trim_and_cast(uint32_t n, uint32_t padded, uint32_t dims, const uint16_t
 }
 
 }  // extern "C"
+#pragma GCC visibility pop
 
 // ---- trainer snapshot (host-only code of the product: csrc/snapshot_msgpack.h) --------------------------------
 #include "../../tiny-cuda-nn_amd/csrc/snapshot_msgpack.h"
 
+#pragma GCC visibility push(default)
 extern "C" {
 
 // Encodes a snapshot from host arrays; returns the byte count (call with out == nullptr to size the buffer).
@@ -431,3 +466,4 @@ int emu_snapshot_decode(const uint8_t* data, size_t size, uint64_t* meta, float*
 }
 
 }  // extern "C"
+#pragma GCC visibility pop

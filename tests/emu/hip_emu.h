@@ -46,9 +46,15 @@ inline hipError_t hipMemsetAsync(void* p, int value, size_t bytes, hipStream_t) 
 
 namespace emu {
 
-typedef _Float16 eh8 __attribute__((ext_vector_type(8)));
-typedef _Float16 eh4 __attribute__((ext_vector_type(4)));
-typedef _Float16 eh2 __attribute__((ext_vector_type(2)));
+// the 16-bit type follows the build, as in csrc/tcnn_device.h: IEEE half, or bfloat16 with -DTCNN_BF16 (libtcnn_emu_bf16.so)
+#if defined(TCNN_BF16)
+typedef __bf16 eh;
+#else
+typedef _Float16 eh;
+#endif
+typedef eh eh8 __attribute__((ext_vector_type(8)));
+typedef eh eh4 __attribute__((ext_vector_type(4)));
+typedef eh eh2 __attribute__((ext_vector_type(2)));
 typedef float ef4 __attribute__((ext_vector_type(4)));
 
 struct Fiber {
@@ -250,13 +256,13 @@ inline uint32_t atomicMax(uint32_t* addr, uint32_t v) {
 
 namespace tcnn_hip {
 
-typedef _Float16 half_t;
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef ::emu::eh half_t;
+typedef half_t h2 __attribute__((ext_vector_type(2)));
+typedef half_t h4 __attribute__((ext_vector_type(4)));
+typedef half_t h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-// v_mfma_f32_16x16x32_f16:  A[i][k]: lane = i + 16*(k/8), element k%8;  B[k][n]: lane = n + 16*(k/8);
+// v_mfma_f32_16x16x32_f16 / _bf16 (products of two 16-bit values are exact in fp32 for either type):  A[i][k]: lane = i + 16*(k/8), element k%8;  B[k][n]: lane = n + 16*(k/8);
 // D[row][col]: lane = col + 16*(row/4), element row%4.
 inline f4 mfma_16x16x32(h8 a, h8 b, f4 c) {
 	const unsigned lane = ::emu::g.cur->tidx.x & 63u;
@@ -276,7 +282,7 @@ inline f4 mfma_16x16x32(h8 a, h8 b, f4 c) {
 	return d;
 }
 
-// v_mfma_f32_16x16x16_f16: 4 halves per lane, k = 4*(lane>>4) + j
+// v_mfma_f32_16x16x16_f16 / bf16_1k: 4 halves per lane, k = 4*(lane>>4) + j
 inline f4 mfma_16x16x16(h4 a, h4 b, f4 c) {
 	const unsigned lane = ::emu::g.cur->tidx.x & 63u;
 	::emu::Wave& w = ::emu::g.waves[::emu::g.cur->tidx.x / 64];
@@ -301,7 +307,7 @@ inline f4 mfma_16x16x16(h4 a, h4 b, f4 c) {
 }
 
 // ds_read_b64_tr_b16: lane c of a 16-lane group, element j <- element (c & 3) of the word lane 4j + (c >> 2) addressed
-inline h4 lds_read_tr4(const _Float16* word) {
+inline h4 lds_read_tr4(const half_t* word) {
 	const unsigned lane = ::emu::g.cur->tidx.x & 63u;
 	::emu::Wave& w = ::emu::g.waves[::emu::g.cur->tidx.x / 64];
 	h8 mine = {};
@@ -315,7 +321,35 @@ inline h4 lds_read_tr4(const _Float16* word) {
 	return out;
 }
 
-inline _Float16 emu_round_h(double v) { return (_Float16)v; }  // double -> half is a single RNE rounding
+#if defined(TCNN_BF16)
+// double -> bfloat16 in ONE rounding (RNE), written out in integer arithmetic so that it does not depend on how the host compiler
+// lowers the conversion (through fp32 it would round twice): the double is first brought to fp32 with ROUND-TO-ODD (truncate towards
+// zero, set the last bit if anything was lost -- 16 spare bits below bfloat16's last one, so the sticky bit cannot reach a tie), then
+// fp32 -> bfloat16 rounds to nearest even on the bit pattern.
+inline half_t emu_round_h(double v) {
+	float f = (float)v;
+	uint32_t b;
+	if (v != v) return (half_t)__builtin_nanf("");
+	if ((double)f != v) {  // inexact (or overflowed to infinity: then the largest finite fp32, odd already, rounds up to infinity below)
+		if (__builtin_fabs((double)f) > __builtin_fabs(v)) f = __builtin_nextafterf(f, 0.0f);
+		memcpy(&b, &f, 4);
+		b |= 1u;
+	} else {
+		memcpy(&b, &f, 4);
+	}
+	if ((b & 0x7F800000u) != 0x7F800000u) b += 0x7FFFu + ((b >> 16) & 1u);
+	const uint16_t h = (uint16_t)(b >> 16);
+	half_t out;
+	memcpy(&out, &h, 2);
+	return out;
+}
+// global_atomic_pk_add_bf16 / ds_pk_add_bf16: the exact sum rounded once.  The fp64 sum of two bfloat16 values is either exact (exponents
+// less than ~45 apart) or within one fp64 ulp of the larger operand -- 44 bits below the nearest bfloat16 tie -- so rounding IT once to
+// bfloat16 equals rounding the exact sum.  tests/test_emu_bf16.py::test_packed_atomic_add_rounds_once compares this function with exact
+// rational arithmetic on ties, near-ties, subnormals and overflow.
+#else
+inline half_t emu_round_h(double v) { return (half_t)v; }  // double -> half is a single RNE rounding
+#endif
 
 inline void atomic_add_h2(half_t* addr, h2 v) {
 	addr[0] = emu_round_h((double)addr[0] + (double)v[0]);
@@ -326,10 +360,16 @@ inline void lds_atomic_add_f32(float* addr, float v) { *addr = *addr + v; }
 inline void lds_atomic_add_u64(unsigned long long* addr, unsigned long long v) { *addr = *addr + v; }
 inline void lds_atomic_add_h2(h2* addr, h2 v) { atomic_add_h2((half_t*)addr, v); }
 inline uint32_t atomic_add_u32(uint32_t* addr, uint32_t v) { const uint32_t old = *addr; *addr = old + v; return old; }
+#if defined(TCNN_BF16)
+// as on the device (tcnn_device.h): gfx950 has no bf16 fma, the chain is an fp32 fma rounded to bfloat16
+inline half_t fma_h(half_t a, half_t b, half_t c) { return (half_t)__builtin_fmaf((float)a, (float)b, (float)c); }
+inline h2 fma_h2(h2 a, h2 b, h2 c) { return h2{fma_h(a[0], b[0], c[0]), fma_h(a[1], b[1], c[1])}; }
+#else
 inline h2 fma_h2(h2 a, h2 b, h2 c) {
 	return h2{emu_round_h((double)a[0] * (double)b[0] + (double)c[0]), emu_round_h((double)a[1] * (double)b[1] + (double)c[1])};
 }
 inline half_t fma_h(half_t a, half_t b, half_t c) { return emu_round_h((double)a * (double)b + (double)c); }
+#endif
 inline uint32_t xcc_id() { return ::emu::g.bidx.x & 7u; }
 
 }  // namespace tcnn_hip

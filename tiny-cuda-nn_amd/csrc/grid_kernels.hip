@@ -928,6 +928,15 @@ TCNN_DEVICE h2 bits_h2(uint32_t v) { return __builtin_bit_cast(h2, v); }
 //   the level's slices, with a factor 8 of headroom over that uniform share -- k = 30 - ceil(log2(8 * share)), 20 <= k <= 40.  At the
 //   stress shape: k = 31 - 34 for the hashed levels, resolution 2^-31 and finer against records of 1e-7 and up.  A slice whose records
 //   exceed the headroom (clustered samples) fails the int32 bound test as before and is redone with 64 bits per value at the same k.
+//   What is summed is the magnitude of what the scatter emits: |dL/dy| in the first-order pass (the corner weights of a sample add up to
+//   one), |dL/dy| * sum over the corners of |weight| in the second-order pass, whose weights carry ddx * scale (each sample clamped to
+//   LEVEL_SUM_CLAMP either way).  The sum is kept in 2^-32 units in 64 bits: a workgroup's total is clamped below 2^32 before it is
+//   converted (level_sum_units), and a sum that would pass 2^64 -- 2^20 samples at the clamp -- SATURATES at 2^64 - 1 instead of
+//   wrapping to a small value (level_sum_add, and the sum over the parts in owner_scale): such a level gets the coarsest exponent its
+//   slice count allows (k = 20 for up to 2^26 slices) and never the k = 40 a wrapped sum of zero would have chosen.
+//   Range (bfloat16): a record whose scaled value |v| * 2^k does not stay below 9e18 (~2^63) cannot enter a 64-bit sum and is DROPPED
+//   (to_fixed64).  With k >= 20 every record below 2^42 (4.4e12) is carried; above that the gradient of the entries it touches is not
+//   defined (include/tcnn_hip.h states the range, tests/test_emu_bf16.py pins the edge).
 struct OwnerScale {
 	int k;
 	TCNN_DEVICE float up(float v) const { return HALF_IS_BF16 ? __builtin_ldexpf(v, k) : v * 16777216.0f; }
@@ -938,12 +947,35 @@ struct OwnerScale {
 };
 constexpr uint32_t LEVEL_SUM_PARTS = 8;  // words a level's sum is spread over (the scatter's workgroups add into word blockIdx % 8)
 constexpr float LEVEL_SUM_CLAMP = 4096.0f;  // per sample: 2^18 .. 2^20 samples of it stay inside 64 bits at 2^-32 units
+// a workgroup's fp32 total -> 2^-32 units: clamped below 2^32 first (the conversion of a larger value is undefined), nothing for
+// zero, negative values and NaN
+TCNN_HOST_DEVICE unsigned long long level_sum_units(float total) {
+	if (!(total > 0.0f)) return 0ull;
+	return (unsigned long long)((double)__builtin_fminf(total, 4294967040.0f) * 4294967296.0);  // (the largest fp32 below 2^32)
+}
+TCNN_HOST_DEVICE unsigned long long saturating_add_u64(unsigned long long a, unsigned long long b) {
+	const unsigned long long s = a + b;
+	return s < a ? ~0ull : s;
+}
+// adds into one of a level's sum words; sticky at 2^64 - 1: whoever sees the word wrap sets it to the maximum, and every later add wraps
+// again and does the same (the owners read the word in a later launch, after the last of them)
+TCNN_DEVICE void level_sum_add(unsigned long long* word, unsigned long long units) {
+	if (units == 0ull) return;
+#if defined(TCNN_HOST_EMU)
+	*word = saturating_add_u64(*word, units);
+#else
+	const unsigned long long old = atomicAdd(word, units);
+	if (old + units < old) atomicMax(word, ~0ull);
+#endif
+}
 template <typename PLAN>
 TCNN_DEVICE OwnerScale owner_scale(const PLAN& plan, const uint32_t* counters, uint32_t j) {
 	if constexpr (!HALF_IS_BF16) return OwnerScale{24};
 	unsigned long long sum = 0;
 #pragma unroll
-	for (uint32_t p = 0; p < LEVEL_SUM_PARTS; ++p) sum += *(const unsigned long long*)(counters + plan.level_sum_base + 2u * (plan.sum_slot(j) * LEVEL_SUM_PARTS + p));
+	for (uint32_t p = 0; p < LEVEL_SUM_PARTS; ++p) {
+		sum = saturating_add_u64(sum, *(const unsigned long long*)(counters + plan.level_sum_base + 2u * (plan.sum_slot(j) * LEVEL_SUM_PARTS + p)));
+	}
 	if (sum == 0ull) return OwnerScale{40};
 	const float share = (float)sum * (8.0f / 4294967296.0f) / (float)(plan.n_buckets[j] * plan.n_chunks[j]);
 	int e;
@@ -1049,13 +1081,22 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 		const uint32_t chunk = tile / plan.tiles_per_chunk[j];
 		uint32_t* __restrict__ my_counters = counters + plan.counter_base[j] + chunk * nb;
 
-#if defined(TCNN_BF16)  // the level's sum of |dL/dy| (OwnerScale), gathered per thread over the workgroup's tiles
-#pragma unroll
-		for (uint32_t s = 0; s < SPT; ++s) {
+		// (bfloat16 build) a sample's share of the level's sum that picks the owners' exponent (OwnerScale) starts from max_f |dL/dy|
+		auto max_abs_dy = [&](uint32_t s) {
 			float m = 0.0f;
 #pragma unroll
 			for (uint32_t f = 0; f < F; ++f) m = __builtin_fmaxf(m, __builtin_fabsf((float)g[s][f]));
-			if (tile * TILE + s * BUCKET_THREADS + threadIdx.x < io.n) level_abs_sum += __builtin_fminf(m, LEVEL_SUM_CLAMP);  // (NaN -> the other operand: the bound test sees it)
+			return m;
+		};
+		(void)max_abs_dy;
+#if defined(TCNN_BF16)
+		// first order: the corner weights of a sample add up to one, so the sum of |dL/dy| over the workgroup's tiles is the sum of what is
+		// emitted.  (The second-order pass gathers its sum inside derive() below, where the weights are known.)
+		if constexpr (!second_order) {
+#pragma unroll
+			for (uint32_t s = 0; s < SPT; ++s) {
+				if (tile * TILE + s * BUCKET_THREADS + threadIdx.x < io.n) level_abs_sum += __builtin_fminf(max_abs_dy(s), LEVEL_SUM_CLAMP);  // (NaN -> the other operand: the bound test sees it)
+			}
 		}
 #endif
 		// ---- derive the records of my samples; rank each pair within its bucket
@@ -1070,11 +1111,14 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 #pragma unroll
 				for (uint32_t d = 0; d < D; ++d) dd[d] = 0.0f;
 				if constexpr (second_order) load_ddx<D>(io, min(tile * TILE + s * BUCKET_THREADS + threadIdx.x, io.n - 1u), dd);
+				float weight_abs_sum = 0.0f;  // (second order, bfloat16 build)
+				(void)weight_abs_sum;
 #pragma unroll
 				for (uint32_t idx = 0; idx < N_CORNERS; ++idx) {
 					float weight;
 					if constexpr (second_order) weight = corner_weight_second_order<D>(lv, c, idx, dd);
 					else weight = lv.nearest ? 1.0f : corner_weight<D>(c, idx);
+					if constexpr (second_order && HALF_IS_BF16) weight_abs_sum += __builtin_fabsf(weight);
 					if constexpr (F == 1) {
 						pay[s][idx][0] = __builtin_bit_cast(uint32_t, weight * (float)g[s][0]);
 					} else {
@@ -1084,6 +1128,11 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 						for (uint32_t p = 0; p < PW; ++p) pay[s][idx][p] = h2_bits(w2 * h2{g[s][2 * p], g[s][2 * p + 1]});
 					}
 					ridx[s][idx] = corner_index<D, FAST>(lv, c, idx);
+				}
+				if constexpr (second_order && HALF_IS_BF16) {
+					// the second-order records are dy * weight with weights of the size of ddx * scale, not of one: the level's sum (OwnerScale) is
+					// taken from what is emitted -- from |dL/dy| alone small ddx left every record below 2^-k and large ones sent every slice wide
+					if (valid) level_abs_sum += __builtin_fminf(max_abs_dy(s) * weight_abs_sum, LEVEL_SUM_CLAMP);
 				}
 				// Hashed levels (prime[0] == 1): the two entries of EVERY pair of a sample differ by the same low bits, x ^ (x + 1) under the table's
 				// mask -- whether a pair's second record can ride with the first (same bucket; derivable from word 0 by construction) and the
@@ -1247,10 +1296,7 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 		if (threadIdx.x == 0) {
 			float total = 0.0f;
 			for (uint32_t w = 0; w < BUCKET_THREADS / WAVE; ++w) total += __builtin_bit_cast(float, part[w]);
-			if (total > 0.0f) {
-				atomicAdd((unsigned long long*)(counters + plan.level_sum_base + 2u * (j * LEVEL_SUM_PARTS + (blockIdx.x % LEVEL_SUM_PARTS))),
-				          (unsigned long long)((double)total * 4294967296.0));
-			}
+			level_sum_add((unsigned long long*)(counters + plan.level_sum_base + 2u * (j * LEVEL_SUM_PARTS + (blockIdx.x % LEVEL_SUM_PARTS))), level_sum_units(total));
 		}
 	}
 #else
@@ -1417,13 +1463,17 @@ __device__ unsigned long long g_owner_wide_slices = 0ull;
 // round(v * 2^k) (OwnerScale; IEEE half: k = 24, |v| < 128); saturates beyond (such a slice fails the bound and is redone in 64 bits).  A
 // 16-bit float times 2^24 is an integer already when the type is IEEE half (11 significant bits, exponent >= -24): the conversion
 // instruction alone (v_cvt_i32_f32 saturates and maps NaN to 0 -- written as asm because the C++ conversion is undefined out of range).
+// The instruction drops the fraction (towards zero): what it is given is an integer already, by the type (IEEE half) or by the rintf.
+// The host emulator runs the same two steps with the instruction restated in C++.
 TCNN_DEVICE int to_fixed32(float v, const OwnerScale& sc) {
-#if defined(TCNN_HOST_EMU)
-	v = __builtin_fminf(__builtin_fmaxf(v, -127.0f), 127.0f);
-	return (int)__builtin_rintf(v * 16777216.0f);
-#else
 	float s = sc.up(v);
 	if constexpr (HALF_IS_BF16) s = __builtin_rintf(s);  // bfloat16 records reach below 2^-k
+#if defined(TCNN_HOST_EMU)
+	if (s != s) return 0;
+	if (s >= 2147483648.0f) return 2147483647;
+	if (s <= -2147483648.0f) return -2147483647 - 1;
+	return (int)s;
+#else
 	int r;
 	asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(s));
 	return r;
