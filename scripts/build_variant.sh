@@ -5,7 +5,7 @@ set -e
 NAME=$1; DEFS=$2
 ROOT=$(cd $(dirname $0)/.. && pwd)
 OBJ=/tmp/tcnn_variant_$NAME; mkdir -p $OBJ $ROOT/tiny-cuda-nn_amd/lib/variants
-for f in $(cd $ROOT/tiny-cuda-nn_amd/csrc && ls *.hip | sed s/.hip$//); do
+for f in $(cd $ROOT/tiny-cuda-nn_amd/csrc && ls *.hip | grep -v '^grid_kernels.hip$' | sed s/.hip$//); do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Wno-unused-function $DEFS -c $ROOT/tiny-cuda-nn_amd/csrc/$f.hip -o $OBJ/$f.o &
 done
 wait

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Static check of the SHIPPED gfx950 code for the hazard ADVICE round 4 names in the owner pass of the grid backward
-(csrc/grid_kernels.hip, bucket_level_packed): its queue stream issues `global_load_dwordx3 ... nt` from inline asm into registers
+(csrc/grid_backward_owner.hip, bucket_level_packed): its queue stream issues `global_load_dwordx3 ... nt` from inline asm into registers
 `grp[][]` and awaits them with counted `s_waitcnt vmcnt(N)` asm statements.  The compiler's own wait-count insertion does not know
 these loads exist, so nothing but the source's discipline stops it from COPYING, SPILLING or REUSING a destination register between the
 issue and the wait (a loop back-edge rotation, a spill under register pressure, another TCNN_OWNER_GROUPS value): such an instruction

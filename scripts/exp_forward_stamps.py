@@ -1,6 +1,6 @@
 """Where the gather's time goes, per XCD and level: k_grid_forward_tiles stamped per workgroup (100 MHz wall clock at entry and exit, level, XCD slot).
 The instrumentation is NOT in the tree; scripts/exp_forward_stamps.patch adds it to a working copy:
-    git apply scripts/exp_forward_stamps.patch && bash scripts/build_variant_one.sh stampfwd grid_kernels "" && git apply -R scripts/exp_forward_stamps.patch
+    git apply scripts/exp_forward_stamps.patch && bash scripts/build_variant_one.sh stampfwd grid_forward "" && git apply -R scripts/exp_forward_stamps.patch
     TCNN_HIP_LIBRARY=$PWD/tiny-cuda-nn_amd/lib/variants/stampfwd.so python scripts/exp_forward_stamps.py
 Results: profiles/r04_exp_notes.txt section 18."""
 import ctypes as C

@@ -1,7 +1,7 @@
 """Where an owner workgroup's time goes: per-workgroup wall-clock stamps (100 MHz) written by an instrumented build of k_grid_bucket_owner
 (stamps at entry / before and after the table-clear barrier / after the queue stream / after the second barrier / after conversion +
 stores / after the sign-off).  The instrumentation is NOT in the tree; scripts/exp_owner_stamps.patch adds it to a working copy:
-    git apply scripts/exp_owner_stamps.patch && bash scripts/build_variant_one.sh stamps grid_kernels "" && git apply -R scripts/exp_owner_stamps.patch
+    git apply scripts/exp_owner_stamps.patch && bash scripts/build_variant_one.sh stamps grid_backward_owner "" && git apply -R scripts/exp_owner_stamps.patch
     TCNN_HIP_LIBRARY=$PWD/tiny-cuda-nn_amd/lib/variants/stamps.so python scripts/exp_owner_stamps.py
 Results: profiles/r04_exp_notes.txt section 14."""
 import ctypes as C

@@ -1,6 +1,6 @@
 """The record scatter under a clock: k_grid_bucket_scatter stamped per workgroup (entry, first tile loaded, end of each of its first four tiles, level).
 The instrumentation is NOT in the tree; scripts/exp_scatter_stamps.patch adds it to a working copy:
-    git apply scripts/exp_scatter_stamps.patch && bash scripts/build_variant_one.sh stampsc grid_kernels "" && git apply -R scripts/exp_scatter_stamps.patch
+    git apply scripts/exp_scatter_stamps.patch && bash scripts/build_variant_one.sh stampsc grid_backward_scatter "" && git apply -R scripts/exp_scatter_stamps.patch
     TCNN_HIP_LIBRARY=$PWD/tiny-cuda-nn_amd/lib/variants/stampsc.so python scripts/exp_scatter_stamps.py
 Results: profiles/r04_exp_notes.txt section 15."""
 import ctypes as C

@@ -2,7 +2,7 @@
 plain numpy over the oracle, nothing here touches the emulator or the GPU library.
 
 u = 2^-9 is the unit the bars are written in.  bfloat16 has 8 significant bits: ONE rounding to nearest moves a value by up to
-2^-8 of its magnitude = 2 u.  The bucketed backward's fixed-point rule (grid_kernels.hip, OwnerScale): a record v enters a slice's
+2^-8 of its magnitude = 2 u.  The bucketed backward's fixed-point rule (grid_backward_plan.h, OwnerScale): a record v enters a slice's
 sum as round(v * 2^k), k = 30 - ceil(log2(8 * share)) clamped to 20..40, share = (level's sum over the samples of
 min(record magnitude of the sample, 4096)) / (slices x chunks of the level); at most half a unit 2^-k is lost per record."""
 import math

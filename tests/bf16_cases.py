@@ -216,7 +216,7 @@ def test_stress_shape_training_step_at_its_stated_size():
         a, b = gq[nm + off[l]:nm + off[l + 1]], gref[nm + off[l]:nm + off[l + 1]]
         assert rel(a, b) < 5e-2, (l, rel(a, b))
         # Untouched entries stay exactly zero on both sides (the optimizer skips them, adam.h:79-82).  Touched ones: the owner pass sums bfloat16
-        # records in fixed point at an exponent chosen per slice from the level's own |dL/dy| (OwnerScale, grid_kernels.hip) -- 2^-28 on the
+        # records in fixed point at an exponent chosen per slice from the level's own |dL/dy| (OwnerScale, grid_backward_plan.h) -- 2^-28 on the
         # hashed levels of this step, so a sum survives unless it is below 2^-29 = 2.5e-5 of the level's rms (round 5: 2^-24 for every level,
         # i.e. everything below 8e-4 of the rms vanished, and the test accepted zeros up to 2 % of it).  Tables of 2^19 entries and more have
         # one owner per slice: a zero where the oracle holds more than 1e-4 of the rms is a sample whose dL/dy differs between the two sides
@@ -246,7 +246,7 @@ def test_stress_shape_training_step_at_its_stated_size():
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Grid backward and second order across bfloat16's range, in the bucketed mode (the library's default, set explicitly).  Bars as in
-# tests/test_emu_bf16.py (helpers: tests/bf16_bars.py), per level from the plan rule the library documents (grid_kernels.hip,
+# tests/test_emu_bf16.py (helpers: tests/bf16_bars.py), per level from the plan rule the library documents (grid_backward_plan.h,
 # make_backward_plan), restated here from the test's own sizes:
 #   * a slice is the largest power-of-two number of entries whose 64-bit-per-value table fits the default 128 KiB of LDS;
 #   * a level's samples are split into chunks only when a slice would see more than 65536 records (n * 2^D / slices):

@@ -228,7 +228,7 @@ def grid_backward_plan(g, n, mode=BUCKETED, accumulate=False, lds_budget=0):
 
 
 def level_sum_units(total):
-    """level_sum_units() of grid_kernels.hip: a workgroup's fp32 total of clamped |record| -> 2^-32 units in 64 bits"""
+    """level_sum_units() of grid_backward_plan.h: a workgroup's fp32 total of clamped |record| -> 2^-32 units in 64 bits"""
     fn = lib().emu_level_sum_units
     fn.restype = C.c_uint64
     return int(fn(C.c_float(total)))

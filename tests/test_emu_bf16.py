@@ -7,7 +7,7 @@ rounding to nearest moves a value by up to half a unit in the last place = 2^-8 
 from ref at a tie).  `absacc` is the oracle's backward of |dL/dy| (the sum of the magnitudes an entry accumulated), N_e the number of
 records of an entry.
 
-The fixed-point rule the bucketed backward documents (grid_kernels.hip, OwnerScale): a record v enters a slice's sum as
+The fixed-point rule the bucketed backward documents (grid_backward_plan.h, OwnerScale): a record v enters a slice's sum as
 round(v * 2^k), k = 30 - ceil(log2(8 * share)) clamped to 20..40, share = (level's sum of min(|record magnitude per sample|, 4096))
 / (slices x chunks of the level).  `owner_k` restates that rule from the test's inputs and the host plan's slice counts; at most
 half a unit 2^-k is lost per record: floor_e = N_e * 2^-(k+1).
@@ -283,7 +283,7 @@ def test_grid_bucket_owner_forms_agree_over_the_range(case, magnitude, lds_budge
 
 
 def test_grid_backward_record_range_edge():
-    """The documented range of the bfloat16 bucketed backward (include/tcnn_hip.h, OwnerScale in grid_kernels.hip): a record whose scaled
+    """The documented range of the bfloat16 bucketed backward (include/tcnn_hip.h, OwnerScale in grid_backward_plan.h): a record whose scaled
     value |v| * 2^k reaches 9e18 cannot enter a 64-bit sum and is dropped; k >= 20, so every record below 2^42 is carried.  One sample in
     the middle of a cell (all four corner weights 1/4, four distinct entries): dL/dy = 2^43 gives records of 2^41 -- carried exactly;
     dL/dy = 2^46 gives records of 2^44 = 2^64 units at k = 20 -- dropped: the entries read zero (not Inf, not garbage), in all three

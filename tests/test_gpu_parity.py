@@ -947,7 +947,7 @@ def test_bucketed_grid_backward_full_size(clustered):
 @pytest.mark.parametrize("log2_t,scale", [(15, 1.5), (19, 2.0)])
 def test_owner_pass_hand_pipelined_stream_at_every_queue_length(log2_t, scale):
     """The packed owner pass streams its queues through loads the compiler does not see (inline asm into registers that keep their
-    identity, counted s_waitcnt: csrc/grid_kernels.hip bucket_level_packed).  That path is compiled out of the host
+    identity, counted s_waitcnt: csrc/grid_backward_owner.hip bucket_level_packed).  That path is compiled out of the host
     emulator, so it is pinned here: batch sizes from 256 to 2^17 + 768 give the queues of the sixteen levels every kind of length -- empty
     (fine levels at small batches), shorter than one round of a lane, a few records more or less than whole rounds of 4 x NG x 512
     records -- and the gradients must equal, BIT FOR BIT, the 64-bit-per-value owner kernel's (mode 1: plain C++ loads, no pipelining)

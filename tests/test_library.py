@@ -349,7 +349,7 @@ def test_no_mfma_result_is_read_too_soon_after_a_taken_branch(tmp_path, build):
 @pytest.mark.parametrize("lib_name", ["libtcnn_hip.so", "libtcnn_hip_bf16.so"])
 def test_no_register_of_a_hand_issued_load_is_touched_before_its_wait(tmp_path, lib_name):
     """The owner pass of the grid backward streams its queues through loads issued from inline asm and awaited with counted
-    `s_waitcnt vmcnt(N)` statements (csrc/grid_kernels.hip, bucket_level_packed): the compiler's wait-count insertion does not know these
+    `s_waitcnt vmcnt(N)` statements (csrc/grid_backward_owner.hip, bucket_level_packed): the compiler's wait-count insertion does not know these
     loads, so a register copy, spill or reuse between issue and wait would read data that is still in flight -- silently wrong gradients on the
     GPU, invisible to the emulator, which compiles the path out.  scripts/check_asm_load_hazard.py follows EVERY
     control-flow path of the SHIPPED code object from each such load and demands a sufficient wait before anything names its destination

@@ -1,6 +1,6 @@
 // adam_device.h -- Adam's per-parameter arithmetic (optimizers/adam.h:48-127), shared by the stand-alone optimizer kernel
 // (elementwise_kernels.hip) and the grid backward's owner pass, which can apply the step straight from the exact gradient
-// sums it holds in LDS (grid_kernels.hip).
+// sums it holds in LDS (grid_backward_owner.hip).
 #pragma once
 #include "tcnn_device.h"
 

@@ -3,16 +3,17 @@
 // Restates the BEHAVIOUR of reference include/tiny-cuda-nn/encodings/grid.h:49-349 (kernel_grid,
 // kernel_grid_backward, kernel_grid_backward_input) and common_device.h:767-895,1000-1043 with an
 // MI355X-first mapping:
-//   * one (level, sample-tile) work item per workgroup, and workgroup -> level chosen so that the
-//     workgroups an XCD receives (block b runs on XCD b%8) all walk the same one or two levels: a
-//     level's table (<= 2^log2_hashmap_size * F * 2 B, 2 MiB at the headline config) then stays in
-//     that XCD's private 4 MiB L2 while it is being gathered / scattered.  Placement only changes
-//     speed, never results.
-//   * the per-level scale/resolution come from a host-computed table (bit-exact indices on any
-//     device), the interpolation is the reference's fp16 fma chain (v_pk_fma_f16) -> bit-exact
-//     encodings versus the CPU oracle.
-//   * backward: packed-half atomics (global_atomic_pk_add_f16) for large levels; levels whose whole
-//     table fits in LDS are accumulated per workgroup in fp32 LDS (ds_add_f32) and flushed once.
+//   * forward (grid_forward.hip): one (level, sample-tile) work item per workgroup; the items are laid end to end, weighted by what a
+//     level costs, and cut into eight runs, one per XCD (block b runs on XCD b % 8), so that an XCD walks one or two tables at a time and
+//     they stay in its private 4 MiB L2.  Placement only changes speed, never results.
+//   * the per-level scale / resolution come from a host-computed table (bit-exact indices on any device), the interpolation is the
+//     reference's fp16 fma chain (v_pk_fma_f16): encodings bit-exact against the CPU oracle.
+//   * backward, the Bucketed mode (the default): pass A derives every corner record once and appends it to the queue of the workgroup
+//     that owns its slice of the table (grid_backward_scatter.hip); pass B, the owners, sum their queues in fixed point in LDS and store
+//     the slice -- exact, order-independent, no float atomics, no memset (grid_backward_owner.*).  Levels the bucket plan does not take
+//     and the SlicedF32 / SlicedF16 modes (A/B measurements) run the sliced owner-computes kernel, which re-derives the corners per
+//     slice; the Atomic mode is the reference's formulation and the fallback for stochastic interpolation (grid_backward.hip).
+//   * shared by all of them: grid_device.h (level / cell arithmetic), grid_backward_plan.h (the host plan of the backward passes).
 #pragma once
 #include "tcnn_device.h"
 
@@ -54,10 +55,10 @@ void grid_forward(hipStream_t stream, const GridMeta& meta, const GridIO& io, co
 // Backward into grid_gradient (half).  accumulate == false overwrites (GradientMode::Overwrite: any zeroing
 // the chosen mode needs is done here, the caller does not memset), true adds to what is there.
 //   SlicedF32 / SlicedF16: owner-computes LDS accumulation (fp32, or packed fp16 like the reference's own
-//                          half2 atomics) -- no global atomics on large levels; the default.
-//   Atomic:                the reference's formulation, global_atomic_pk_add_f16 per corner (F >= 2 only);
-//                          kept for A/B measurements.
-//   Bucketed:              large levels derive every corner ONCE, bin the records by owning slice in HBM queues
+//                          half2 atomics) -- no global atomics on large levels; kept for A/B measurements.
+//   Atomic:                the reference's formulation, global_atomic_pk_add_f16 per corner; what stochastic interpolation
+//                          and second-order scatters outside the bucket plan fall back to.
+//   Bucketed:              the default (api_switches.hip).  Large levels derive every corner ONCE, bin the records by owning slice in HBM queues
 //                          and let the owner accumulate them in 64-bit fixed point in LDS; small levels as in
 //                          the sliced modes.  Needs a GridBackwardWorkspace (sizes from grid_backward_workspace_size):
 //                          `scratch` is device memory the call may scribble on (nothing is kept in it between
