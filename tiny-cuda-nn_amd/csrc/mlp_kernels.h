@@ -1,4 +1,7 @@
-// mlp_kernels.h -- fully fused MLP (16/32/64/128 wide, fp16 storage, fp32 MFMA accumulation) on gfx950.
+// mlp_kernels.h -- the MLP on gfx950 (16-bit storage, fp32 MFMA accumulation): fully fused kernels for 16/32/64/128 neurons, and a
+// layer-by-layer network (mlp_general.hip, the reference's CutlassMLP) for every other multiple of 16 up to MLP_GENERAL_MAX_WIDTH.
+// Both sit behind the same launchers (mlp_forward / mlp_backward / ...) with the same parameter and boundary layouts; what follows
+// describes the fused kernels.
 //
 // Restates the BEHAVIOUR of reference src/fully_fused_mlp.cu:499-837 (kernel_mlp_fused,
 // kernel_mlp_fused_backward and the four CUTLASS call sites :786,:820,:829,:835) -- not its tiling.
@@ -29,7 +32,7 @@ namespace tcnn_hip {
 
 struct MlpMeta {
 	uint32_t in_width;          // multiple of 16
-	uint32_t width;             // 16 / 32 / 64 / 128
+	uint32_t width;             // 16 / 32 / 64 / 128 (fused kernels), or any other multiple of 16 <= MLP_GENERAL_MAX_WIDTH (layer by layer)
 	uint32_t padded_out;        // multiple of 16, <= MLP_MAX_OUT_WIDTH
 	uint32_t n_hidden_matmuls;  // n_hidden_layers - 1
 	uint32_t activation;        // Activation of the hidden layers
@@ -78,6 +81,11 @@ TCNN_HOST_DEVICE uint32_t mlp_wave_slab_param(const MlpMeta& m, uint32_t positio
 constexpr uint32_t MLP_MAX_HIDDEN_MATMULS_TRAIN = 3;  // the register-resident backward / training kernels are instantiated for 0..3
 constexpr uint32_t MLP_MAX_IN_WIDTH = 128;
 constexpr uint32_t MLP_MAX_OUT_WIDTH = 128;  // padded; more than 16 outputs train through the layer-by-layer backward
+// the layer-by-layer network of the other widths (mlp_general.hip)
+constexpr uint32_t MLP_GENERAL_MAX_WIDTH = 1024;
+constexpr uint32_t MLP_GENERAL_MAX_IN_WIDTH = 1024;
+// the widths the fused kernels are instantiated for; every other one takes the layer-by-layer path
+TCNN_HOST_DEVICE bool mlp_fused_width(uint32_t width) { return width == 16u || width == 32u || width == 64u || width == 128u; }
 
 // Forward.  hidden == nullptr -> inference (nothing saved).
 void mlp_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, half_t* hidden,
@@ -86,7 +94,8 @@ void mlp_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t*
 // weights -> transposed scratch ([in_width][W] | HM x [W][W] | [W][16]); n_params halves
 void mlp_transpose_weights(hipStream_t stream, const MlpMeta& m, const half_t* params, half_t* params_t);
 
-// Number of fp32 partial gradient slabs mlp_backward writes (== its grid size) for batch n.
+// Number of fp32 partial gradient slabs mlp_backward writes for batch n (fused widths: its grid size; other widths: the batch slices
+// of the weight-gradient products, mlp_general_n_partials).
 uint32_t mlp_backward_n_partials(const MlpMeta& m, uint32_t n);
 
 // dL/d(pre-activation of the output layer) from dL/doutput and the (post-activation) output; only needed when the
@@ -97,8 +106,8 @@ void mlp_output_activation_backward(hipStream_t stream, const MlpMeta& m, uint32
 // Backward.  dL_doutput is the gradient w.r.t. the output layer's PRE-activation (== dL/doutput when the output
 // activation is None).  params_t from mlp_transpose_weights.  dL_dinput may be null.  partials: fp32
 // [mlp_backward_n_partials][n_params] or null (GradientMode::Ignore).
-// Networks with more than MLP_MAX_HIDDEN_MATMULS_TRAIN + 1 hidden layers run a layer-by-layer formulation that
-// needs `workspace` (mlp_backward_workspace_bytes, 0 for the shallower ones).
+// Networks with more than MLP_MAX_HIDDEN_MATMULS_TRAIN + 1 hidden layers, and every network of a width outside 16/32/64/128, run a
+// layer-by-layer formulation that needs `workspace` (mlp_backward_workspace_bytes, 0 for the others).
 size_t mlp_backward_workspace_bytes(const MlpMeta& m, uint32_t n);
 void mlp_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params_t, const half_t* input, const half_t* hidden,
                   const half_t* dL_doutput, half_t* dL_dinput, float* partials, void* workspace = nullptr);
@@ -106,7 +115,8 @@ void mlp_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t
 // Fused training pass of Trainer::training_step (trainer.h:254-357): forward + loss + backward per sample tile in one
 // kernel -- the hidden activations stay in LDS, prediction / dL_doutput are written for the caller's ForwardContext
 // (either may be null), block_sums receives mlp_backward_n_partials() partial loss sums.  Bit-identical to
-// mlp_forward -> loss_evaluate -> mlp_backward.  Widths 16/32/64 (and 128 through mlp_train_wide), up to 4 hidden layers (mlp_train_supported).
+// mlp_forward -> loss_evaluate -> mlp_backward.  Widths 16/32/64 (and 128 through mlp_train_wide), up to 4 hidden layers (mlp_train_supported);
+// never the layer-by-layer widths (mlp_train_wave_supported, mlp_train_wide_supported and mlp_infer_wave_supported name their widths too).
 struct MlpLossArgs {
 	LossType type;
 	const float* targets;   // fp32 [n][dims]
@@ -173,5 +183,15 @@ SlabOrder mlp_train(hipStream_t stream, const MlpMeta& m, uint32_t n, const half
 // `order`: how the slabs are laid out -- what mlp_train() returned for them (mlp_backward writes parameter order)
 void mlp_finalize_gradients(hipStream_t stream, const MlpMeta& m, uint32_t n_partials, const float* partials, half_t* grads, bool accumulate,
                             SlabOrder order = SlabOrder::Params);
+
+// ---- widths outside 16/32/64/128 (mlp_general.hip): one launch per layer and direction, one per weight matrix.  mlp_forward /
+// mlp_backward / mlp_backward_n_partials / mlp_backward_workspace_bytes route here by width; same contracts.  With hidden == nullptr the
+// forward pass keeps two ping-pong activation matrices in stream-ordered scratch of its own.  No fused training pass: mlp_train_supported
+// is false for these widths, so a training step is forward (saved activations) -> loss -> backward.
+void mlp_general_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, half_t* hidden, half_t* output);
+uint32_t mlp_general_n_partials(const MlpMeta& m, uint32_t n);
+size_t mlp_general_backward_workspace_bytes(const MlpMeta& m, uint32_t n);
+void mlp_general_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params_t, const half_t* input, const half_t* hidden,
+                          const half_t* dL_doutput, half_t* dL_dinput, float* partials, void* workspace);
 
 }  // namespace tcnn_hip

@@ -995,14 +995,17 @@ __global__ void __launch_bounds__(32 * FINALIZE_GROUPS) k_mlp_finalize_gradients
 // host launchers
 // =============================================================================================
 static void check_meta(const MlpMeta& m, uint32_t n) {
-	if (m.width != 16 && m.width != 32 && m.width != 64 && m.width != 128) {
-		throw std::runtime_error("FullyFusedMLP only supports 16, 32, 64, and 128 neurons, but got " + std::to_string(m.width) + ".");
+	const bool fused = mlp_fused_width(m.width);
+	if (!fused && (m.width < 16 || m.width > MLP_GENERAL_MAX_WIDTH || m.width % 16 != 0)) {
+		throw std::runtime_error("MLP: the number of neurons must be a multiple of 16 between 16 and " + std::to_string(MLP_GENERAL_MAX_WIDTH) + ", but got " +
+		                         std::to_string(m.width) + ".");
 	}
-	if (m.in_width % 16 != 0 || m.in_width == 0 || m.in_width > MLP_MAX_IN_WIDTH) {
-		throw std::runtime_error("FullyFusedMLP: input width must be a multiple of 16 and at most " + std::to_string(MLP_MAX_IN_WIDTH) + ".");
+	const uint32_t max_in = fused ? MLP_MAX_IN_WIDTH : MLP_GENERAL_MAX_IN_WIDTH;
+	if (m.in_width % 16 != 0 || m.in_width == 0 || m.in_width > max_in) {
+		throw std::runtime_error(std::string(fused ? "FullyFusedMLP" : "MLP") + ": input width must be a multiple of 16 and at most " + std::to_string(max_in) + ".");
 	}
 	if (m.padded_out % 16 != 0 || m.padded_out == 0 || m.padded_out > MLP_MAX_OUT_WIDTH) {
-		throw std::runtime_error("FullyFusedMLP: at most " + std::to_string(MLP_MAX_OUT_WIDTH) + " output dimensions are supported.");
+		throw std::runtime_error(std::string(fused ? "FullyFusedMLP" : "MLP") + ": at most " + std::to_string(MLP_MAX_OUT_WIDTH) + " output dimensions are supported.");
 	}
 	if (n % BATCH_SIZE_GRANULARITY != 0) throw std::runtime_error("Batch size must be a multiple of 256.");
 }
@@ -1030,6 +1033,10 @@ static void launch_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, con
 void mlp_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, half_t* hidden, half_t* output) {
 	check_meta(m, n);
 	if (n == 0) return;
+	if (!mlp_fused_width(m.width)) {
+		mlp_general_forward(stream, m, n, params, input, hidden, output);
+		return;
+	}
 	if (!hidden && mlp_infer_wave_supported(m, n)) {
 		mlp_infer_wave(stream, m, n, params, input, output);
 		return;
@@ -1047,7 +1054,7 @@ void mlp_transpose_weights(hipStream_t stream, const MlpMeta& m, const half_t* p
 }
 
 uint32_t mlp_backward_n_partials(const MlpMeta& m, uint32_t n) {
-	(void)m;
+	if (!mlp_fused_width(m.width)) return mlp_general_n_partials(m, n);
 	const uint32_t n_tiles = n / MLP_BWD_TILE;
 #ifndef TCNN_MLP_PARTIALS
 #define TCNN_MLP_PARTIALS 512
@@ -1120,6 +1127,7 @@ static void dispatch_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, 
 }
 
 size_t mlp_backward_workspace_bytes(const MlpMeta& m, uint32_t n) {
+	if (!mlp_fused_width(m.width)) return mlp_general_backward_workspace_bytes(m, n);
 	const bool layer_by_layer = m.n_hidden_matmuls > MLP_MAX_HIDDEN_MATMULS_TRAIN || m.padded_out != 16;
 	return layer_by_layer ? (size_t)(m.n_hidden_matmuls + 1) * n * m.width * sizeof(half_t) : 0;
 }
@@ -1128,6 +1136,10 @@ void mlp_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t
                   const half_t* dL_doutput, half_t* dL_dinput, float* partials, void* workspace) {
 	check_meta(m, n);
 	if (n == 0) return;
+	if (!mlp_fused_width(m.width)) {
+		mlp_general_backward(stream, m, n, params_t, input, hidden, dL_doutput, dL_dinput, partials, workspace);
+		return;
+	}
 	switch (m.width) {
 		case 16: dispatch_backward<16>(stream, m, n, params_t, input, hidden, dL_doutput, dL_dinput, partials, workspace); break;
 		case 32: dispatch_backward<32>(stream, m, n, params_t, input, hidden, dL_doutput, dL_dinput, partials, workspace); break;
@@ -1177,6 +1189,7 @@ uint32_t mlp_train_n_partials(const MlpMeta& m, uint32_t n, LossType loss) {
 }
 
 bool mlp_train_supported(const MlpMeta& m) {
+	if (!mlp_fused_width(m.width)) return false;  // the layer-by-layer widths: forward with saved activations -> loss -> backward
 	// 128-wide networks: k_mlp_train measured no faster than the three-kernel path (the weight-gradient accumulators of four
 	// 128 x 128 matrices spill at 64-sample tiles); they have their own kernel (mlp_train_wide.hip) for 32 / 64 inputs
 	if (m.width == 128) return mlp_train_wide_supported(m, MLP_BWD_TILE);
@@ -1224,3 +1237,8 @@ void mlp_finalize_gradients(hipStream_t stream, const MlpMeta& m, uint32_t n_par
 }
 
 }  // namespace tcnn_hip
+
+// the layer-by-layer network is a unit of its own in the library (csrc/Makefile); the host emulator's unity build gets it through this file
+#if defined(TCNN_HOST_EMU)
+#include "mlp_general.hip"
+#endif

@@ -191,7 +191,7 @@ EncodingDesc create_encoding_desc(uint32_t n_dims, const Json& enc, uint32_t ali
 
 Json NetworkDesc::hyperparams() const {
 	Json j = Json::object();
-	j["otype"] = "FullyFusedMLP";
+	j["otype"] = mlp_fused_width(mlp.width) ? "FullyFusedMLP" : "CutlassMLP";  // fully_fused_mlp.h:141, cutlass_mlp.h:152
 	j["activation"] = to_string((Activation)mlp.activation);
 	j["output_activation"] = to_string((Activation)mlp.output_activation);
 	j["n_neurons"] = mlp.width;
@@ -207,12 +207,23 @@ static NetworkDesc create_network_desc(uint32_t n_input_dims, uint32_t n_output_
 	NetworkDesc d;
 	d.otype = otype;
 	const uint32_t n_neurons = net.value("n_neurons", 128u);
-	if (n_neurons != 16 && n_neurons != 32 && n_neurons != 64 && n_neurons != 128) {
+	// network.cu:51-77, 129-137: FullyFusedMLP exists for four widths; "MLP" / "CutlassMLP" take those where they can and the
+	// layer-by-layer network (mlp_general.hip) for every other multiple of 16
+	const bool fused = mlp_fused_width(n_neurons);
+	const bool wants_fused = equals_case_insensitive(otype, "MegakernelMLP") || equals_case_insensitive(otype, "FullyFusedMLP");
+	if (!fused && wants_fused) {
 		throw std::runtime_error("FullyFusedMLP only supports 16, 32, 64, and 128 neurons, but got " + std::to_string(n_neurons) +
-		                         ". (CutlassMLP's arbitrary widths are not part of this build.)");
+		                         ". Use CutlassMLP instead.");
 	}
+	if (!fused && n_neurons % 16 != 0) {
+		throw std::runtime_error("CutlassMLP: the number of neurons must be a multiple of 16, but got " + std::to_string(n_neurons) + ".");
+	}
+	if (!fused && (n_neurons < 16 || n_neurons > MLP_GENERAL_MAX_WIDTH)) {
+		throw std::runtime_error("CutlassMLP: between 16 and " + std::to_string(MLP_GENERAL_MAX_WIDTH) + " neurons are supported by this build, but got " + std::to_string(n_neurons) + ".");
+	}
+	const char* const name = fused ? "FullyFusedMLP" : "CutlassMLP";
 	d.n_hidden_layers = net.value("n_hidden_layers", 5u);
-	if (d.n_hidden_layers == 0) throw std::runtime_error("FullyFusedMLP requires at least 1 hidden layer (3 layers in total).");
+	if (d.n_hidden_layers == 0) throw std::runtime_error(std::string(name) + " requires at least 1 hidden layer (3 layers in total).");
 	const Activation act = string_to_activation(net.value("activation", "ReLU"));
 	const Activation out_act = string_to_activation(net.value("output_activation", "None"));
 	d.n_output_dims = n_output_dims;
@@ -223,10 +234,11 @@ static NetworkDesc create_network_desc(uint32_t n_input_dims, uint32_t n_output_
 	d.mlp.activation = (uint32_t)act;
 	d.mlp.output_activation = (uint32_t)out_act;
 	if (d.mlp.padded_out > MLP_MAX_OUT_WIDTH) {
-		throw std::runtime_error("FullyFusedMLP: more than " + std::to_string(MLP_MAX_OUT_WIDTH) + " output dimensions are not supported by this build.");
+		throw std::runtime_error(std::string(name) + ": more than " + std::to_string(MLP_MAX_OUT_WIDTH) + " output dimensions are not supported by this build.");
 	}
-	if (n_input_dims % 16 != 0 || n_input_dims > MLP_MAX_IN_WIDTH) {
-		throw std::runtime_error("FullyFusedMLP: input width " + std::to_string(n_input_dims) + " must be a multiple of 16 and at most " + std::to_string(MLP_MAX_IN_WIDTH));
+	const uint32_t max_in = fused ? MLP_MAX_IN_WIDTH : MLP_GENERAL_MAX_IN_WIDTH;
+	if (n_input_dims % 16 != 0 || n_input_dims > max_in) {
+		throw std::runtime_error(std::string(name) + ": input width " + std::to_string(n_input_dims) + " must be a multiple of 16 and at most " + std::to_string(max_in));
 	}
 	return d;
 }
