@@ -119,6 +119,11 @@ int tcnn_module_grid_indices(tcnn_module_t* m, tcnn_stream_t stream, uint32_t n_
 /* Grid layout accessors used by the reference's own known-answer test (tests/test_grid.cu:55-71). */
 int tcnn_module_grid_level_n_params(const tcnn_module_t* m, uint32_t level, size_t* out);
 int tcnn_module_grid_level_params_offset(const tcnn_module_t* m, uint32_t level, size_t* out);
+/* Layout of a Composite encoding (composite.h; 0 nested encodings for every other module).  layout[0..3]: the first input dimension the
+ * nested encoding reads, its input width, the first row of the (unreduced) encoded matrix it writes, its padded output width;
+ * params[0..1]: where its parameters start behind the network's (if any) and how many it has. */
+uint32_t tcnn_module_n_nested(const tcnn_module_t* m);
+int tcnn_module_nested_layout(const tcnn_module_t* m, uint32_t index, uint32_t* layout, size_t* params);
 
 /* ---- create_from_config / Trainer / Network::inference (C++ template API) ------------------------ */
 /* tcnn::create_from_config, config.h:53-63.  config_json holds "loss", "optimizer", "encoding", "network". */

@@ -49,6 +49,19 @@ public:
 	Type type() const { return m_type; }
 	bool is_object() const { return m_type == Type::Object; }
 	bool is_null() const { return m_type == Type::Null; }
+	// arrays (the "nested" list of a Composite encoding): walk with size() / operator[](index), build with push_back
+	bool is_array() const { return m_type == Type::Array; }
+	size_t size() const { return m_type == Type::Array ? m_arr.size() : m_type == Type::Object ? m_obj.size() : 0; }
+	const Json& operator[](size_t index) const {
+		if (m_type != Type::Array) throw std::runtime_error("JSON: not an array (looking up element " + std::to_string(index) + ")");
+		if (index >= m_arr.size()) throw std::runtime_error("JSON: array index " + std::to_string(index) + " out of range");
+		return m_arr[index];
+	}
+	void push_back(const Json& v) {
+		if (m_type == Type::Null) m_type = Type::Array;
+		if (m_type != Type::Array) throw std::runtime_error("JSON: not an array (push_back)");
+		m_arr.push_back(v);
+	}
 
 	bool contains(const std::string& key) const { return m_type == Type::Object && m_obj.count(key) > 0; }
 	const Json& operator[](const std::string& key) const {

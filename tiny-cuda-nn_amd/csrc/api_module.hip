@@ -125,7 +125,7 @@ int tcnn_module_backward(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_cont
 int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_, const tcnn_context_t* ctx, uint32_t n, const float* dL_ddLdinput,
                                         const float* input, const void* dL_doutput, void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput,
                                         const void* params) {
-	if (m->md.has_network || !m->md.enc.is_grid) {
+	if (m->md.has_network || !m->md.enc.is_grid()) {
 		set_last_error("DifferentiableObject::backward_backward_input_impl: not implemented error");  // object.h:478
 		return TCNN_ERROR_UNSUPPORTED;
 	}
@@ -224,21 +224,34 @@ int tcnn_module_set_jit_fusion(tcnn_module_t*, int val) {
 
 int tcnn_module_grid_indices(tcnn_module_t* m, tcnn_stream_t stream, uint32_t n, const float* input, uint32_t* indices) {
 	TCNN_API_BEGIN
-	if (!m->md.enc.is_grid) throw std::runtime_error("grid_indices: module has no grid encoding");
+	if (!m->md.enc.is_grid()) throw std::runtime_error("grid_indices: module has no grid encoding");
 	GridIO io = {input, m->md.n_input_dims, 1u, n, n, 1u};
 	grid_indices((hipStream_t)stream, m->md.enc.grid, io, indices);
 	TCNN_API_END
 }
 int tcnn_module_grid_level_n_params(const tcnn_module_t* m, uint32_t level, size_t* out) {
 	TCNN_API_BEGIN
-	if (!m->md.enc.is_grid || level >= m->md.enc.grid.n_levels) throw std::runtime_error("grid_level_n_params: invalid level");
+	if (!m->md.enc.is_grid() || level >= m->md.enc.grid.n_levels) throw std::runtime_error("grid_level_n_params: invalid level");
 	*out = m->md.enc.grid.offset[level + 1] - m->md.enc.grid.offset[level];  // multi_level_interface.h level_n_params
 	TCNN_API_END
 }
 int tcnn_module_grid_level_params_offset(const tcnn_module_t* m, uint32_t level, size_t* out) {
 	TCNN_API_BEGIN
-	if (!m->md.enc.is_grid || level >= m->md.enc.grid.n_levels) throw std::runtime_error("grid_level_params_offset: invalid level");
+	if (!m->md.enc.is_grid() || level >= m->md.enc.grid.n_levels) throw std::runtime_error("grid_level_params_offset: invalid level");
 	*out = m->md.enc.grid.offset[level];
+	TCNN_API_END
+}
+uint32_t tcnn_module_n_nested(const tcnn_module_t* m) { return (uint32_t)m->md.enc.nested.size(); }
+int tcnn_module_nested_layout(const tcnn_module_t* m, uint32_t index, uint32_t* layout, size_t* params) {
+	TCNN_API_BEGIN
+	if (index >= m->md.enc.nested.size()) throw std::runtime_error("nested_layout: invalid index");
+	const EncodingDesc& e = m->md.enc.nested[index];
+	layout[0] = e.dims_to_encode_begin;
+	layout[1] = e.n_dims;
+	layout[2] = e.output_row;
+	layout[3] = e.padded_output_width;
+	params[0] = m->md.n_mlp_params() + e.param_offset;
+	params[1] = e.n_params;
 	TCNN_API_END
 }
 

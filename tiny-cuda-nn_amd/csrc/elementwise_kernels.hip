@@ -4,6 +4,7 @@
 #include "elementwise_kernels.h"
 #include <type_traits>
 #include "adam_device.h"
+#include "encoding_device.h"
 
 #include <cmath>
 
@@ -693,13 +694,7 @@ void adam_convert_step_representation(hipStream_t stream, uint32_t n, uint32_t s
 	}
 }
 
-// The element-wise encodings write their value type VAL_T: the library's 16-bit type (rounded to nearest even, as the reference's
-// (T) casts do), or float for the fp32 encodings of create_encoding(..., Precision::Fp32) (Encoding<float>, cpp_api.cu:165-168).
-template <typename VAL_T>
-TCNN_DEVICE VAL_T encoded_value(float v) {
-	if constexpr (std::is_same<VAL_T, float>::value) return v;
-	else return to_half_rn(v);
-}
+// The per-element arithmetic of the encodings below lives in encoding_device.h (shared with the fused kernels of composite_kernels.hip).
 // ------------------------------------------------------------------------------------------ identity
 template <typename VAL_T>
 __global__ void k_identity_forward(uint32_t n, uint32_t n_dims, uint32_t padded, float scale, float offset, const float* __restrict__ in,
@@ -712,9 +707,7 @@ __global__ void k_identity_forward(uint32_t n, uint32_t n_dims, uint32_t padded,
 	if (k >= n_dims) {
 		v = (VAL_T)1.0f;  // identity.h:62-64
 	} else {
-		float t = in[(size_t)i * in_stride_i + (size_t)k * in_stride_j] * scale;
-		t = t + offset;
-		v = encoded_value<VAL_T>(t);
+		v = encoded_value<VAL_T>(identity_value(in[(size_t)i * in_stride_i + (size_t)k * in_stride_j], scale, offset));
 	}
 	out[(size_t)k * stride_k + (size_t)i * stride_i] = v;
 }
@@ -736,17 +729,13 @@ __global__ void __launch_bounds__(EW_THREADS) k_identity_forward_transpose(uint3
 			const f4 v = *(const f4*)(src + e);
 #pragma unroll
 			for (uint32_t j = 0; j < 4; ++j) {
-				float t = v[j] * scale;
-				t = t + offset;
-				tile[(k + j) * ID_LD + s] = to_half_rn(t);
+				tile[(k + j) * ID_LD + s] = to_half_rn(identity_value(v[j], scale, offset));
 			}
 		}
 	} else {
 		for (uint32_t e = threadIdx.x; e < rows * n_dims; e += EW_THREADS) {
 			const uint32_t s = e / n_dims, k = e - s * n_dims;
-			float t = src[e] * scale;
-			t = t + offset;
-			tile[k * ID_LD + s] = to_half_rn(t);
+			tile[k * ID_LD + s] = to_half_rn(identity_value(src[e], scale, offset));
 		}
 	}
 	__syncthreads();
@@ -769,8 +758,7 @@ __global__ void k_identity_backward(uint32_t n, uint32_t n_dims, float scale, co
 	const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
 	if (e >= n * n_dims) return;
 	const uint32_t k = e / n, i = e - k * n;
-	// identity.h:83: (T)((float)dL_dy * scale) -- rounded through half, then widened to the fp32 dL_dx
-	dL_dx[(size_t)i * dx_stride_i + (size_t)k * dx_stride_j] = (float)encoded_value<VAL_T>((float)dL_dy[(size_t)k * stride_k + (size_t)i * stride_i] * scale);
+	dL_dx[(size_t)i * dx_stride_i + (size_t)k * dx_stride_j] = identity_dL_dx<VAL_T>(dL_dy[(size_t)k * stride_k + (size_t)i * stride_i], scale);
 }
 
 void identity_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t padded, float scale, float offset, const float* in,
@@ -806,7 +794,6 @@ void identity_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, float sc
 // with the argument, up to 2^11 pi here); this kernel and the oracle evaluate sinf / cosf of the SAME fp32 argument
 // x 2^f * pi + phase, so parity with the reference is to its intrinsic's accuracy (a fp16 ulp at these magnitudes), parity
 // between kernel and oracle to libm rounding.  One thread per output element (k-major, i fastest).
-#define TCNN_PI_F 3.14159265358979323846f
 template <typename VAL_T>
 __global__ void __launch_bounds__(EW_THREADS) k_frequency_forward(uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* __restrict__ in,
                                                                   uint32_t in_stride_i, uint32_t in_stride_j, VAL_T* __restrict__ out, uint32_t stride_k,
@@ -816,11 +803,8 @@ __global__ void __launch_bounds__(EW_THREADS) k_frequency_forward(uint32_t n, ui
 	const uint32_t j = e / n, i = e - j * n;
 	VAL_T v = (VAL_T)1.0f;
 	if (j < n_dims * n_frequencies * 2u) {
-		const uint32_t d = j / (n_frequencies * 2u), log2_frequency = (j / 2u) % n_frequencies;
-		const float phase_shift = (float)(j % 2u) * (TCNN_PI_F / 2);
-		const float x = __builtin_scalbnf(in[(size_t)i * in_stride_i + (size_t)d * in_stride_j], (int)log2_frequency);
-		const float input = x * TCNN_PI_F + phase_shift;
-		v = encoded_value<VAL_T>(sinf(input));
+		const uint32_t d = j / (n_frequencies * 2u);
+		v = encoded_value<VAL_T>(frequency_value(in[(size_t)i * in_stride_i + (size_t)d * in_stride_j], j - d * n_frequencies * 2u));
 	}
 	out[(size_t)j * stride_k + (size_t)i * stride_i] = v;
 }
@@ -832,15 +816,7 @@ __global__ void __launch_bounds__(EW_THREADS) k_frequency_backward(uint32_t n, u
 	if (e >= n * n_dims) return;
 	const uint32_t d = e / n, i = e - d * n, outputs_per_input = n_frequencies * 2u;
 	const float x0 = in[(size_t)i * in_stride_i + (size_t)d * in_stride_j];
-	float result = 0;
-	for (uint32_t k = 0; k < outputs_per_input; ++k) {
-		const uint32_t j = d * outputs_per_input + k, log2_frequency = k / 2u;
-		const float phase_shift = (float)(k % 2u) * (TCNN_PI_F / 2);
-		const float input = __builtin_scalbnf(x0, (int)log2_frequency) * TCNN_PI_F + phase_shift;
-		const float dy_dx = __builtin_scalbnf(1.0f, (int)log2_frequency) * TCNN_PI_F * cosf(input);  // what the reference's forward pass stores
-		result += (float)dL_dy[(size_t)j * stride_k + (size_t)i * stride_i] * dy_dx;
-	}
-	dL_dx[(size_t)i * dx_stride_i + (size_t)d * dx_stride_j] = result;
+	dL_dx[(size_t)i * dx_stride_i + (size_t)d * dx_stride_j] = frequency_dL_dx<VAL_T>(dL_dy + (size_t)d * outputs_per_input * stride_k + (size_t)i * stride_i, stride_k, n_frequencies, x0);
 }
 template <typename VAL_T>
 static void frequency_forward_t(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
@@ -876,18 +852,6 @@ void frequency_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_
 // ------------------------------------------------------------------------------------------ one-blob
 // encodings/oneblob.h:84-164 (the SoA kernels' arithmetic) with common_device.h:1076-1095 (quartic kernel).  One thread per
 // (dimension j, sample i), i fastest: the n_bins bin integrals of a quartic blob centred at x, wrapped around [0, 1).
-TCNN_DEVICE float quartic(float x, float inv_radius) {
-	const float u = x * inv_radius;
-	const float tmp = __builtin_fmaxf(1 - u * u, 0.0f);
-	return ((float)15 / 16) * tmp * tmp;
-}
-TCNN_DEVICE float quartic_cdf_deriv(float x, float inv_radius) { return quartic(x, inv_radius) * inv_radius; }
-TCNN_DEVICE float quartic_cdf(float x, float inv_radius) {
-	const float u = x * inv_radius;
-	const float u2 = u * u;
-	const float u4 = u2 * u2;
-	return __builtin_fmaxf(0.0f, __builtin_fminf(1.0f, ((float)15 / 16) * u * (1 - ((float)2 / 3) * u2 + ((float)1 / 5) * u4) + 0.5f));
-}
 template <typename VAL_T>
 __global__ void __launch_bounds__(EW_THREADS) k_oneblob_forward(uint32_t n, uint32_t n_dims, uint32_t log2_bins, uint32_t padded, const float* __restrict__ in,
                                                                 uint32_t in_stride_i, uint32_t in_stride_j, VAL_T* __restrict__ out, uint32_t stride_k,
@@ -898,10 +862,9 @@ __global__ void __launch_bounds__(EW_THREADS) k_oneblob_forward(uint32_t n, uint
 		const uint32_t j = e / n, i = e - j * n;
 		const float x = in[(size_t)i * in_stride_i + (size_t)j * in_stride_j];
 		const float nb = (float)n_bins, inv_bins = 1.0f / nb;  // scalbnf(k, -log2_bins) == k * inv_bins exactly
-		float left_cdf = quartic_cdf(-x, nb) + quartic_cdf(-x - 1.0f, nb) + quartic_cdf(-x + 1.0f, nb);
+		float left_cdf = oneblob_cdf(oneblob_boundary(x, 0u, inv_bins), nb);
 		for (uint32_t k = 0; k < n_bins; ++k) {
-			const float right_boundary = (float)(k + 1) * inv_bins;
-			const float right_cdf = quartic_cdf(right_boundary - x, nb) + quartic_cdf(right_boundary - x - 1.0f, nb) + quartic_cdf(right_boundary - x + 1.0f, nb);
+			const float right_cdf = oneblob_cdf(oneblob_boundary(x, k + 1u, inv_bins), nb);
 			out[(size_t)(j * n_bins + k) * stride_k + (size_t)i * stride_i] = encoded_value<VAL_T>(right_cdf - left_cdf);
 			left_cdf = right_cdf;
 		}
@@ -918,17 +881,7 @@ __global__ void __launch_bounds__(EW_THREADS) k_oneblob_backward(uint32_t n, uin
 	if (e >= n * n_dims) return;
 	const uint32_t j = e / n, i = e - j * n, n_bins = 1u << log2_bins;
 	const float x = in[(size_t)i * in_stride_i + (size_t)j * in_stride_j];
-	const float nb = (float)n_bins, inv_bins = 1.0f / nb;
-	float result = 0;
-	float left_cdf = quartic_cdf_deriv(-x, nb) + quartic_cdf_deriv(-x - 1.0f, nb) + quartic_cdf_deriv(-x + 1.0f, nb);
-	for (uint32_t k = 0; k < n_bins; ++k) {
-		const float right_boundary = (float)(k + 1) * inv_bins;
-		const float right_cdf = quartic_cdf_deriv(right_boundary - x, nb) + quartic_cdf_deriv(right_boundary - x - 1.0f, nb) + quartic_cdf_deriv(right_boundary - x + 1.0f, nb);
-		const float deriv = left_cdf - right_cdf;
-		left_cdf = right_cdf;
-		result += (float)dL_dy[(size_t)(j * n_bins + k) * stride_k + (size_t)i * stride_i] * deriv;
-	}
-	dL_dx[(size_t)i * dx_stride_i + (size_t)j * dx_stride_j] = result;
+	dL_dx[(size_t)i * dx_stride_i + (size_t)j * dx_stride_j] = oneblob_dL_dx<VAL_T>(dL_dy + (size_t)j * n_bins * stride_k + (size_t)i * stride_i, stride_k, n_bins, x);
 }
 
 template <typename VAL_T>

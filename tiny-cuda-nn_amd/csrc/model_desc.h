@@ -4,17 +4,22 @@
 // for the HashGrid + FullyFusedMLP hot path only.
 #pragma once
 #include <string>
+#include <vector>
 
 #include "../../include/tiny-cuda-nn/json_mini.h"
 #include "adam_device.h"
+#include "composite_kernels.h"
 #include "elementwise_kernels.h"
 #include "grid_kernels.h"
 #include "mlp_kernels.h"
 
 namespace tcnn_hip {
 
+enum class EncodingKind : uint32_t { Identity = 0, OneBlob = 1, Frequency = 2, TriangleWave = 3, Grid = 4, Composite = 5 };
+enum class ReductionType : uint32_t { Concatenation = 0, Sum = 1, Product = 2 };  // common.h ReductionType
+
 struct EncodingDesc {
-	bool is_grid = false;
+	EncodingKind kind = EncodingKind::Identity;
 	// grid (grid.h:673-737)
 	GridMeta grid = {};
 	uint32_t log2_hashmap_size = 19, base_resolution = 16;
@@ -22,18 +27,31 @@ struct EncodingDesc {
 	// identity (identity.h:88-93)
 	float id_scale = 1.0f, id_offset = 0.0f;
 	// one-blob (oneblob.h:168-178): n_bins outputs per input dimension
-	bool is_oneblob = false;
 	uint32_t n_bins = 0;
-	// frequency (frequency.h:106-111): sin and cos of n_frequencies octaves per input dimension
-	bool is_frequency = false;
+	// frequency (frequency.h:106-111): sin and cos of n_frequencies octaves per input dimension; triangle wave (triangle_wave.h:113-116):
+	// one output per octave
 	uint32_t n_frequencies = 0;
 	uint32_t n_dims = 0;
-	uint32_t n_output_dims = 0;  // before padding
+	uint32_t n_output_dims = 0;  // before padding (a Composite's: its padded width, composite.h:374-376)
 	uint32_t n_params = 0;
 	uint32_t padded_output_width = 0;
+	// composite (composite.h:138-212): the nested encodings in order.  Each one carries its own place in the composite: the first
+	// input dimension it reads, the first row of the (unreduced) encoded matrix it writes -- n_dims and padded_output_width are its
+	// input and padded output width -- and where its parameters start behind the composite's first one.
+	ReductionType reduction = ReductionType::Concatenation;
+	std::vector<EncodingDesc> nested;
+	uint32_t dims_to_encode_begin = 0, output_row = 0, param_offset = 0;
 
-	uint32_t required_output_alignment() const { return is_grid ? grid.n_feat : 1u; }  // grid.h:1066-1068
+	// the top-level encoding is a single grid: what level groups, the LDS budget, grid_level_* / grid_indices, second-order gradients
+	// and the optimizer's per-level deficits apply to.  Grids nested in a Composite take the plain path.
+	bool is_grid() const { return kind == EncodingKind::Grid; }
+	bool is_composite() const { return kind == EncodingKind::Composite; }
+	bool has_nested_grid() const;
+	uint32_t unreduced_width() const { return reduction == ReductionType::Concatenation ? padded_output_width : padded_output_width * (uint32_t)nested.size(); }
+	uint32_t required_output_alignment() const;  // grid.h:1066-1068, composite.h:394-400
 	void set_alignment(uint32_t alignment);  // encoding.h:70-72
+	void set_padded_output_width(uint32_t width);  // composite.h:382-392
+	const char* name() const;
 	Json hyperparams() const;
 };
 
@@ -57,7 +75,7 @@ struct Model {
 	size_t n_params() const { return n_mlp_params() + enc.n_params; }  // network first, then encoding (:115-122)
 	uint32_t padded_output_width() const { return has_network ? net.mlp.padded_out : enc.padded_output_width; }
 	uint32_t output_width() const { return has_network ? net.n_output_dims : enc.padded_output_width; }
-	std::string name() const { return has_network ? "NetworkWithInputEncoding" : (enc.is_grid ? "GridEncoding" : (enc.is_oneblob ? "OneBlobEncoding" : (enc.is_frequency ? "FrequencyEncoding" : "IdentityEncoding"))); }
+	std::string name() const { return has_network ? "NetworkWithInputEncoding" : enc.name(); }
 
 	void finish();  // fills hyper_json
 	// network_with_input_encoding.h:124-130 + fully_fused_mlp.cu:868-893 + grid.h:1076-1079

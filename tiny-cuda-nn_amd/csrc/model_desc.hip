@@ -48,21 +48,75 @@ static Activation string_to_activation(const std::string& s) {  // common_host.c
 	throw std::runtime_error("Invalid activation name: " + s);  // common_host.cu:94
 }
 
-void EncodingDesc::set_alignment(uint32_t alignment) {
-	uint32_t a = alignment, b = required_output_alignment();
+static uint32_t lcm(uint32_t a, uint32_t b) {
 	uint32_t x = a, y = b;
 	while (y) {
 		uint32_t t = x % y;
 		x = y;
 		y = t;
 	}
-	const uint32_t l = a / x * b;
-	padded_output_width = next_multiple(n_output_dims, l);
+	return a / x * b;
+}
+
+bool EncodingDesc::has_nested_grid() const {
+	for (const EncodingDesc& e : nested) {
+		if (e.is_grid()) return true;
+	}
+	return false;
+}
+
+uint32_t EncodingDesc::required_output_alignment() const {
+	if (is_grid()) return grid.n_feat;  // grid.h:1066-1068
+	uint32_t alignment = 1;
+	for (const EncodingDesc& e : nested) alignment = lcm(alignment, e.required_output_alignment());  // composite.h:394-400
+	return alignment;
+}
+
+void EncodingDesc::set_padded_output_width(uint32_t width) {
+	if (!is_composite()) {
+		if (width < n_output_dims) throw std::runtime_error(std::string(name()) + ": the padded output width " + std::to_string(width) + " is below the output width " + std::to_string(n_output_dims));
+		padded_output_width = width;
+		return;
+	}
+	if (nested.empty()) return;
+	if (reduction == ReductionType::Concatenation) {  // composite.h:383-386: the last nested encoding takes the padding
+		const uint32_t prev_n_dims = padded_output_width - nested.back().padded_output_width;
+		if (width < prev_n_dims) throw std::runtime_error("CompositeEncoding: the padded output width is below the width of the leading nested encodings");
+		nested.back().set_padded_output_width(width - prev_n_dims);
+		padded_output_width = width;
+	} else {  // composite.h:388-390
+		for (uint32_t i = 0; i < nested.size(); ++i) {
+			nested[i].set_padded_output_width(width);
+			nested[i].output_row = i * width;
+		}
+		padded_output_width = width;
+	}
+	n_output_dims = padded_output_width;  // composite.h:374-376
+}
+
+void EncodingDesc::set_alignment(uint32_t alignment) {
+	const uint32_t l = lcm(alignment, required_output_alignment());
+	if (is_composite()) {
+		set_padded_output_width(next_multiple(padded_output_width, l));
+	} else {
+		padded_output_width = next_multiple(n_output_dims, l);
+	}
+}
+
+const char* EncodingDesc::name() const {
+	switch (kind) {
+		case EncodingKind::Grid: return "GridEncoding";
+		case EncodingKind::OneBlob: return "OneBlobEncoding";
+		case EncodingKind::Frequency: return "FrequencyEncoding";
+		case EncodingKind::TriangleWave: return "TriangleWaveEncoding";
+		case EncodingKind::Composite: return "CompositeEncoding";
+		default: return "IdentityEncoding";
+	}
 }
 
 Json EncodingDesc::hyperparams() const {
 	Json j = Json::object();
-	if (is_grid) {  // grid.h:1115-1132
+	if (is_grid()) {  // grid.h:1115-1132
 		j["otype"] = "Grid";
 		j["type"] = to_string((GridType)grid.grid_type);
 		j["n_levels"] = grid.n_levels;
@@ -72,12 +126,20 @@ Json EncodingDesc::hyperparams() const {
 		j["interpolation"] = to_string((InterpolationType)grid.interp);
 		j["hash"] = "CoherentPrime";
 		if ((GridType)grid.grid_type == GridType::Hash) j["log2_hashmap_size"] = log2_hashmap_size;
-	} else if (is_frequency) {  // frequency.h:200-205
+	} else if (kind == EncodingKind::Frequency) {  // frequency.h:200-205
 		j["otype"] = "Frequency";
 		j["n_frequencies"] = n_frequencies;
-	} else if (is_oneblob) {  // oneblob.h:296-301
+	} else if (kind == EncodingKind::TriangleWave) {  // triangle_wave.h:205-210
+		j["otype"] = "TriangleWave";
+		j["n_frequencies"] = n_frequencies;
+	} else if (kind == EncodingKind::OneBlob) {  // oneblob.h:296-301
 		j["otype"] = "OneBlob";
 		j["n_bins"] = n_bins;
+	} else if (is_composite()) {  // composite.h:439-449 (no "reduction" key, as there)
+		Json list = Json::array();
+		for (const EncodingDesc& e : nested) list.push_back(e.hyperparams());
+		j["otype"] = "Composite";
+		j["nested"] = list;
 	} else {
 		j["otype"] = "Identity";
 		j["scale"] = id_scale;
@@ -88,7 +150,7 @@ Json EncodingDesc::hyperparams() const {
 
 static EncodingDesc create_grid_encoding(uint32_t n_dims, const Json& enc) {  // grid.h:1725-1852
 	EncodingDesc e;
-	e.is_grid = true;
+	e.kind = EncodingKind::Grid;
 	e.n_dims = n_dims;
 	const std::string hash = enc.value("hash", "CoherentPrime");
 	if (!equals_case_insensitive(hash, "CoherentPrime")) throw std::runtime_error("GridEncoding: compiled without " + hash + " hash support.");
@@ -155,35 +217,170 @@ static EncodingDesc create_grid_encoding(uint32_t n_dims, const Json& enc) {  //
 	return e;
 }
 
+static ReductionType string_to_reduction_type(const std::string& s) {  // common_host.cu:220-232
+	if (equals_case_insensitive(s, "Concatenation")) return ReductionType::Concatenation;
+	if (equals_case_insensitive(s, "Sum")) return ReductionType::Sum;
+	if (equals_case_insensitive(s, "Product")) return ReductionType::Product;
+	throw std::runtime_error("Invalid reduction type: " + s);
+}
+
+static EncodingDesc create_composite_encoding(uint32_t n_dims, const Json& params) {  // composite.h:138-212
+	if (!params.contains("nested") || !params["nested"].is_array()) {
+		throw std::runtime_error("Must provide an array of nested encodings to CompositeEncoding.");
+	}
+	EncodingDesc c;
+	c.kind = EncodingKind::Composite;
+	c.n_dims = n_dims;
+	c.reduction = string_to_reduction_type(params.value("reduction", "Concatenation"));
+	const Json& nested = params["nested"];
+
+	uint32_t total_nested_dims_to_encode = 0;
+	for (size_t i = 0; i < nested.size(); ++i) {
+		total_nested_dims_to_encode += nested[i].value("n_dims_to_encode", 0u);
+		if (nested[i].contains("dims_to_encode_begin")) {
+			total_nested_dims_to_encode = 0xFFFFFFFFu;
+			break;
+		}
+	}
+	if (total_nested_dims_to_encode != 0xFFFFFFFFu && total_nested_dims_to_encode > n_dims) {
+		throw std::runtime_error("CompositeEncoding: nested encodings must not encode more dims " + std::to_string(total_nested_dims_to_encode) + " than composite " +
+		                         std::to_string(n_dims));
+	}
+	uint32_t unspecified_dims_to_encode = total_nested_dims_to_encode == 0xFFFFFFFFu ? 0xFFFFFFFFu : (n_dims - total_nested_dims_to_encode);
+	uint32_t offset = 0;
+	for (size_t i = 0; i < nested.size(); ++i) {
+		uint32_t nested_dims_to_encode;
+		if (nested[i].contains("n_dims_to_encode")) {
+			if (nested[i].contains("dims_to_encode_begin")) offset = (uint32_t)nested[i]["dims_to_encode_begin"].as_number();
+			nested_dims_to_encode = (uint32_t)nested[i]["n_dims_to_encode"].as_number();
+		} else {
+			if (unspecified_dims_to_encode == 0xFFFFFFFFu) {
+				throw std::runtime_error("CompositeEncoding: may only leave 'n_dims_to_encode' unspecified for a single nested encoding");
+			}
+			nested_dims_to_encode = unspecified_dims_to_encode;
+			unspecified_dims_to_encode = 0xFFFFFFFFu;
+		}
+		if (nested_dims_to_encode > 0) {
+			const std::string otype = nested[i].value("otype", "OneBlob");
+			if (equals_case_insensitive(otype, "Composite") || equals_case_insensitive(otype, "NRC") || equals_case_insensitive(otype, "OneBlobFrequency")) {
+				throw std::runtime_error("CompositeEncoding: a nested Composite encoding is not supported by this build (flatten the nested list)");
+			}
+			if ((uint64_t)offset + nested_dims_to_encode > n_dims) {
+				throw std::runtime_error("CompositeEncoding: nested encoding " + std::to_string(i) + " reads dims [" + std::to_string(offset) + ", " +
+				                         std::to_string((uint64_t)offset + nested_dims_to_encode) + ") of a composite with " + std::to_string(n_dims) + " dims");
+			}
+			EncodingDesc e = create_encoding_desc(nested_dims_to_encode, nested[i], 1);
+			e.dims_to_encode_begin = offset;
+			c.nested.push_back(e);
+		}
+		offset += nested_dims_to_encode;
+	}
+	// the reference lets a later nested encoding overwrite the dL_dinput rows of an earlier one that reads the same dims; refused here
+	for (size_t i = 0; i < c.nested.size(); ++i) {
+		for (size_t j = 0; j < i; ++j) {
+			const EncodingDesc &a = c.nested[j], &b = c.nested[i];
+			if (a.dims_to_encode_begin < b.dims_to_encode_begin + b.n_dims && b.dims_to_encode_begin < a.dims_to_encode_begin + a.n_dims) {
+				throw std::runtime_error("CompositeEncoding: nested encodings " + std::to_string(j) + " and " + std::to_string(i) +
+				                         " read overlapping input dims (dims_to_encode_begin); overlapping ranges are not supported by this build");
+			}
+		}
+	}
+	uint32_t n_parameterless = 0;
+	for (const EncodingDesc& e : c.nested) n_parameterless += e.is_grid() ? 0u : 1u;
+	if (n_parameterless > ENCODING_MAX_PARTS) {  // they run as ONE launch driven by a table that travels in the kernel arguments
+		throw std::runtime_error("CompositeEncoding: more than " + std::to_string(ENCODING_MAX_PARTS) + " nested encodings without parameters are not supported by this build");
+	}
+	uint32_t param_offset = 0;
+	for (EncodingDesc& e : c.nested) {  // composite.h:416-422
+		e.param_offset = param_offset;
+		param_offset += e.n_params;
+	}
+	c.n_params = param_offset;
+	// composite.h:188-211: every nested output starts at a multiple of its required alignment
+	if (c.reduction == ReductionType::Concatenation) {
+		uint32_t dims_encoded_so_far = 0;
+		for (size_t i = 0; i < c.nested.size(); ++i) {
+			EncodingDesc& e = c.nested[i];
+			if (i + 1 < c.nested.size()) {
+				const uint32_t desired_alignment = c.nested[i + 1].required_output_alignment();
+				e.set_padded_output_width(next_multiple(dims_encoded_so_far + e.padded_output_width, desired_alignment) - dims_encoded_so_far);
+			}
+			e.output_row = dims_encoded_so_far;
+			dims_encoded_so_far += e.padded_output_width;
+		}
+		c.padded_output_width = dims_encoded_so_far;
+	} else {
+		const uint32_t alignment = c.required_output_alignment();
+		for (EncodingDesc& e : c.nested) e.set_alignment(alignment);
+		for (size_t i = 0; i < c.nested.size(); ++i) {
+			if (c.nested[i].padded_output_width != c.nested[0].padded_output_width) {
+				throw std::runtime_error("CompositeEncoding: a Sum / Product reduction needs nested encodings of equal output width, but nested 0 has " +
+				                         std::to_string(c.nested[0].padded_output_width) + " and nested " + std::to_string(i) + " has " + std::to_string(c.nested[i].padded_output_width));
+			}
+			c.nested[i].output_row = (uint32_t)i * c.nested[0].padded_output_width;
+		}
+		c.padded_output_width = c.nested.empty() ? 0u : c.nested[0].padded_output_width;
+	}
+	c.n_output_dims = c.padded_output_width;  // composite.h:374-376
+	return c;
+}
+
 EncodingDesc create_encoding_desc(uint32_t n_dims, const Json& enc, uint32_t alignment) {  // encoding.cu:131-145
 	const std::string name = enc.value("otype", "OneBlob");
 	EncodingDesc e;
 	if (equals_case_insensitive(name, "Grid") || equals_case_insensitive(name, "HashGrid") || equals_case_insensitive(name, "DenseGrid") ||
 	    equals_case_insensitive(name, "TiledGrid")) {
 		e = create_grid_encoding(n_dims, enc);
+	} else if (equals_case_insensitive(name, "Composite")) {
+		e = create_composite_encoding(n_dims, enc);
+	} else if (equals_case_insensitive(name, "NRC") || equals_case_insensitive(name, "OneBlobFrequency")) {  // encoding.cu:93-115
+		Json tri = Json::object(), blob = Json::object(), rest = Json::object();
+		tri["n_dims_to_encode"] = 3u;
+		tri["otype"] = "TriangleWave";
+		tri["n_frequencies"] = enc.value("n_frequencies", 12u);
+		blob["n_dims_to_encode"] = 5u;
+		blob["otype"] = "OneBlob";
+		blob["n_bins"] = enc.value("n_bins", 4u);
+		rest["otype"] = "Identity";
+		Json list = Json::array();
+		list.push_back(tri);
+		list.push_back(blob);
+		list.push_back(rest);
+		Json composite = Json::object();
+		composite["otype"] = "Composite";
+		composite["nested"] = list;
+		e = create_composite_encoding(n_dims, composite);
 	} else if (equals_case_insensitive(name, "Identity")) {
-		e.is_grid = false;
+		e.kind = EncodingKind::Identity;
 		e.n_dims = n_dims;
 		e.id_scale = enc.value("scale", 1.0f);
 		e.id_offset = enc.value("offset", 0.0f);
 		e.n_output_dims = n_dims;
 		e.padded_output_width = n_dims;
 	} else if (equals_case_insensitive(name, "Frequency")) {  // encoding.cu:65-67
-		e.is_frequency = true;
+		e.kind = EncodingKind::Frequency;
 		e.n_dims = n_dims;
 		e.n_frequencies = enc.value("n_frequencies", 12u);
 		if (e.n_frequencies == 0 || e.n_frequencies > 32) throw std::runtime_error("FrequencyEncoding: n_frequencies must be in [1, 32]");
 		e.n_output_dims = n_dims * e.n_frequencies * 2u;
 		e.padded_output_width = e.n_output_dims;
+	} else if (equals_case_insensitive(name, "TriangleWave")) {  // encoding.cu:89-91
+		e.kind = EncodingKind::TriangleWave;
+		e.n_dims = n_dims;
+		e.n_frequencies = enc.value("n_frequencies", 12u);
+		if (e.n_frequencies == 0 || e.n_frequencies > 32) throw std::runtime_error("TriangleWaveEncoding: n_frequencies must be in [1, 32]");
+		e.n_output_dims = n_dims * e.n_frequencies;
+		e.padded_output_width = e.n_output_dims;
 	} else if (equals_case_insensitive(name, "OneBlob")) {  // encoding.cu:118-120
-		e.is_oneblob = true;
+		e.kind = EncodingKind::OneBlob;
 		e.n_dims = n_dims;
 		e.n_bins = enc.value("n_bins", 16u);
 		if (e.n_bins == 0 || (e.n_bins & (e.n_bins - 1)) != 0) throw std::runtime_error("Number of bins must be a power of 2");  // oneblob.h:174-176
 		e.n_output_dims = n_dims * e.n_bins;
 		e.padded_output_width = e.n_output_dims;
 	} else {
-		throw std::runtime_error("Encoding '" + name + "' not found (this build provides Grid/HashGrid/DenseGrid/TiledGrid, Frequency, OneBlob and Identity)");
+		throw std::runtime_error("Encoding '" + name + "' not found (this build provides Grid/HashGrid/DenseGrid/TiledGrid, Frequency, TriangleWave, OneBlob, Identity, "
+		                         "Composite and its shortcuts NRC/OneBlobFrequency)");
 	}
 	if (alignment > 0) e.set_alignment(alignment);
 	return e;
@@ -274,7 +471,11 @@ void Model::initialize_params(hipStream_t stream, Pcg32& rng, float* params_full
 		HIP_CHECK(hipMemcpyAsync(params_full_precision, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, stream));
 		HIP_CHECK(hipStreamSynchronize(stream));
 	}
-	if (enc.n_params > 0) {
+	if (enc.is_composite()) {  // composite.h:424-429: the nested encodings in order, one rng
+		for (const EncodingDesc& e : enc.nested) {
+			if (e.n_params > 0) generate_random_uniform(stream, rng, e.n_params, params_full_precision + n_mlp_params() + e.param_offset, -1e-4f * scale, 1e-4f * scale);
+		}
+	} else if (enc.n_params > 0) {
 		generate_random_uniform(stream, rng, enc.n_params, params_full_precision + n_mlp_params(), -1e-4f * scale, 1e-4f * scale);
 	}
 }

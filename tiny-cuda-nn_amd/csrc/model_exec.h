@@ -1,6 +1,9 @@
 // model_exec.h -- running a described model: the encoding / network passes over the kernel launchers.  Everything a pass depends on
 // is in its argument list: the stream, the trainer's profiler (null: none), the model and the layout of the caller's matrices.
 #pragma once
+#include <vector>
+
+#include "composite_kernels.h"
 #include "model_desc.h"
 #include "profiler.h"
 #include "scratch_cache.h"
@@ -22,6 +25,10 @@ struct ForwardCtx {
 	Scratch enc;     // half, feature-major [enc.padded][n]   (network_with_input_encoding.h:76)
 	Scratch hidden;  // half [n_hidden][n][width]             (fully_fused_mlp.cu:841-854)
 	Scratch dy_dx;   // fp32 [(k*n + i)*D + d]                (grid.h:783-785)
+	// Composite encoding (composite.h:226-233): the matrix the Sum / Product reduction read (the product's backward needs it), in the value
+	// type and layout of the pass's output with unreduced_width() rows; one dy_dx per nested encoding (allocated for the grids)
+	Scratch unreduced;
+	std::vector<Scratch> nested_dy_dx;
 };
 
 // The grid's parameter gradients in groups of consecutive levels, each reported as soon as its kernels are enqueued (data-parallel
@@ -34,9 +41,10 @@ struct LevelGroups {
 };
 void check_batch(uint32_t n, uint32_t widest = 128);
 uint32_t widest_matrix(const Model& md);  // the widest matrix any pass over `md` indexes, in elements per sample
-// Encoding forward into a feature-major (SoA) or sample-major (AoS) half matrix.
+// Encoding forward into a feature-major (SoA) or sample-major (AoS) half matrix.  dy_dx: a lone grid's; a Composite keeps what its backward
+// pass needs in `ctx` (null: inference), its nested grids' dy_dx when prepare_input_gradients is set.
 void encoding_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const half_t* enc_params, half_t* out,
-                      bool soa, float* dy_dx);
+                      bool soa, float* dy_dx, ForwardCtx* ctx = nullptr, bool prepare_input_gradients = false);
 // the encoding's share of the backward pass: dL_denc has element (feature k, sample i) at [k * stride_k + i * stride_i]
 void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const half_t* dL_denc,
                        uint32_t stride_k, uint32_t stride_i, half_t* dL_dparams, bool want_grads, bool accumulate, const float* input,

@@ -22,9 +22,11 @@ void check_batch(uint32_t n, uint32_t widest) {
 // (feature k, sample i) at [k * stride_k + i * stride_i]
 template <typename T>
 static void parameterless_forward(hipStream_t stream, const EncodingDesc& e, const IoLayout& layout, uint32_t n, const float* input, T* out, uint32_t stride_k, uint32_t stride_i) {
-	if (e.is_frequency) {
+	if (e.kind == EncodingKind::Frequency) {
 		frequency_forward(stream, n, e.n_dims, e.n_frequencies, e.padded_output_width, input, layout.in_stride_i, layout.in_stride_d, out, stride_k, stride_i);
-	} else if (e.is_oneblob) {
+	} else if (e.kind == EncodingKind::TriangleWave) {
+		triangle_wave_forward(stream, n, e.n_dims, e.n_frequencies, e.padded_output_width, input, layout.in_stride_i, layout.in_stride_d, out, stride_k, stride_i);
+	} else if (e.kind == EncodingKind::OneBlob) {
 		oneblob_forward(stream, n, e.n_dims, e.n_bins, e.padded_output_width, input, layout.in_stride_i, layout.in_stride_d, out, stride_k, stride_i);
 	} else {
 		identity_forward(stream, n, e.n_dims, e.padded_output_width, e.id_scale, e.id_offset, input, layout.in_stride_i, layout.in_stride_d, out, stride_k, stride_i);
@@ -33,22 +35,138 @@ static void parameterless_forward(hipStream_t stream, const EncodingDesc& e, con
 template <typename T>
 static void parameterless_backward(hipStream_t stream, const EncodingDesc& e, const IoLayout& layout, uint32_t n, const float* input, const T* dL_dy, uint32_t stride_k, uint32_t stride_i,
                                    float* dL_dinput) {
-	if (e.is_frequency) {
+	if (e.kind == EncodingKind::Frequency) {
 		frequency_backward(stream, n, e.n_dims, e.n_frequencies, dL_dy, stride_k, stride_i, input, layout.in_stride_i, layout.in_stride_d, dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
-	} else if (e.is_oneblob) {
+	} else if (e.kind == EncodingKind::TriangleWave) {
+		triangle_wave_backward(stream, n, e.n_dims, e.n_frequencies, dL_dy, stride_k, stride_i, input, layout.in_stride_i, layout.in_stride_d, dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
+	} else if (e.kind == EncodingKind::OneBlob) {
 		oneblob_backward(stream, n, e.n_dims, e.n_bins, dL_dy, stride_k, stride_i, input, layout.in_stride_i, layout.in_stride_d, dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
 	} else {
 		identity_backward(stream, n, e.n_dims, e.id_scale, dL_dy, stride_k, stride_i, dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
 	}
 }
 
+
+// ---- Composite encoding (composite.h:215-355), T = the 16-bit type or float.  Its nested encodings without parameters are ONE launch driven
+// by a table of parts (composite_kernels.h); every nested grid runs its own kernels on its slice: input dims from dims_to_encode_begin, output
+// rows from output_row, parameters and gradients from param_offset.
+static EncodingParts parameterless_parts(const EncodingDesc& c) {
+	EncodingParts parts;
+	for (const EncodingDesc& e : c.nested) {
+		if (e.is_grid()) continue;
+		EncodingPart p = {};
+		switch (e.kind) {
+			case EncodingKind::Identity: p.kind = PART_IDENTITY; break;
+			case EncodingKind::OneBlob: p.kind = PART_ONEBLOB; p.param = e.n_bins; break;
+			case EncodingKind::Frequency: p.kind = PART_FREQUENCY; p.param = e.n_frequencies; break;
+			case EncodingKind::TriangleWave: p.kind = PART_TRIANGLE_WAVE; p.param = e.n_frequencies; break;
+			default: throw std::runtime_error("CompositeEncoding: unexpected nested encoding");
+		}
+		p.in_row = e.dims_to_encode_begin;
+		p.in_width = e.n_dims;
+		p.out_row = e.output_row;
+		p.padded_width = e.padded_output_width;
+		p.scale = e.id_scale;
+		p.offset = e.id_offset;
+		parts.add(p);
+	}
+	return parts;
+}
+static void nested_grid_forward(hipStream_t stream, const GridMeta& g, const GridIO& io, const half_t* params, half_t* out, float* dy_dx) { grid_forward(stream, g, io, params, out, dy_dx); }
+static void nested_grid_forward(hipStream_t stream, const GridMeta& g, const GridIO& io, const float* params, float* out, float* dy_dx) { grid_forward_f32(stream, g, io, params, out, dy_dx); }
+static void nested_grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_features, const GridIO& io, const half_t* dL_dy, const float* dy_dx, float* dL_dx,
+                                       uint32_t dx_stride_i, uint32_t dx_stride_d) {
+	grid_backward_input(stream, n_dims, n_features, io, dL_dy, dy_dx, dL_dx, dx_stride_i, dx_stride_d);
+}
+static void nested_grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_features, const GridIO& io, const float* dL_dy, const float* dy_dx, float* dL_dx,
+                                       uint32_t dx_stride_i, uint32_t dx_stride_d) {
+	grid_backward_input_f32(stream, n_dims, n_features, io, dL_dy, dy_dx, dL_dx, dx_stride_i, dx_stride_d);
+}
+
+// out: element (feature k, sample i) at [k * stride_k + i * stride_i] with stride_i == 1 (feature-major) or stride_k == 1 (sample-major, stride_i = the padded width)
+template <typename T>
+static void composite_forward(hipStream_t stream, const EncodingDesc& c, const IoLayout& layout, uint32_t n, const float* input, const T* enc_params, T* out, uint32_t stride_k,
+                              uint32_t stride_i, ForwardCtx* ctx, bool prepare_input_gradients) {
+	if (c.nested.empty()) return;
+	const bool reduce = c.reduction != ReductionType::Concatenation;
+	// Sum / Product: the nested encodings write the unreduced matrix (kept in the context: the product's backward pass reads it), in the layout of `out`
+	Scratch unreduced_local;
+	T* target = out;
+	uint32_t target_stride_i = stride_i;
+	if (reduce) {
+		Scratch& u = ctx ? ctx->unreduced : unreduced_local;
+		u = Scratch(stream, (size_t)c.unreduced_width() * n * sizeof(T));
+		target = u.as<T>();
+		if (stride_k == 1u) target_stride_i = c.unreduced_width();
+	}
+	encoding_parts_forward(stream, parameterless_parts(c), n, input, layout.in_stride_i, layout.in_stride_d, target, stride_k, target_stride_i);
+	if (ctx && prepare_input_gradients && c.has_nested_grid()) {
+		ctx->nested_dy_dx.clear();
+		ctx->nested_dy_dx.resize(c.nested.size());
+	}
+	for (size_t idx = 0; idx < c.nested.size(); ++idx) {
+		const EncodingDesc& e = c.nested[idx];
+		if (!e.is_grid()) continue;
+		float* dy_dx = nullptr;
+		if (ctx && prepare_input_gradients) {
+			ctx->nested_dy_dx[idx] = Scratch(stream, (size_t)e.n_output_dims * n * e.n_dims * sizeof(float));
+			dy_dx = ctx->nested_dy_dx[idx].template as<float>();
+		}
+		GridIO io = {input + (size_t)e.dims_to_encode_begin * layout.in_stride_d, layout.in_stride_i, layout.in_stride_d, n, stride_k, target_stride_i};
+		T* rows = target + (size_t)e.output_row * stride_k;
+		nested_grid_forward(stream, e.grid, io, enc_params + e.param_offset, rows, dy_dx);
+		const uint32_t n_to_pad = e.padded_output_width - e.n_output_dims;
+		if (n_to_pad > 0) {  // grid.h:757-766: padded dims are zero
+			if (stride_k == 1u) {
+				HIP_CHECK(hipMemset2DAsync(rows + e.n_output_dims, (size_t)target_stride_i * sizeof(T), 0, (size_t)n_to_pad * sizeof(T), n, stream));
+			} else {
+				HIP_CHECK(hipMemsetAsync(rows + (size_t)e.n_output_dims * stride_k, 0, (size_t)n_to_pad * stride_k * sizeof(T), stream));
+			}
+		}
+	}
+	if (reduce) reduce_forward(stream, c.reduction == ReductionType::Product, n, c.padded_output_width, (uint32_t)c.nested.size(), (const T*)target, stride_k, target_stride_i, out, stride_k, stride_i);
+}
+
+// dL_dinput (when asked for) of the composite; returns the gradient w.r.t. the unreduced matrix and its sample stride for the nested grids' parameter gradients
+template <typename T>
+static const T* composite_backward_input(hipStream_t stream, const EncodingDesc& c, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, uint32_t n_input_dims, float* dL_dinput,
+                                         const T* dL_denc, uint32_t stride_k, uint32_t& stride_i, const float* input, Scratch& dL_dunreduced) {
+	if (c.nested.empty()) return dL_denc;
+	if (c.reduction != ReductionType::Concatenation) {  // composite.h:302-325
+		const bool product = c.reduction == ReductionType::Product;
+		if (product && !ctx.unreduced.ptr) throw std::runtime_error("backward: the forward context holds no unreduced matrix for the product reduction");
+		const uint32_t unreduced_stride_i = stride_k == 1u ? c.unreduced_width() : stride_i;
+		dL_dunreduced = Scratch(stream, (size_t)c.unreduced_width() * n * sizeof(T));
+		reduce_backward(stream, product, n, c.padded_output_width, (uint32_t)c.nested.size(), (const T*)ctx.unreduced.ptr, dL_dunreduced.as<T>(), stride_k, unreduced_stride_i, dL_denc,
+		                stride_k, stride_i);
+		dL_denc = dL_dunreduced.as<T>();
+		stride_i = unreduced_stride_i;
+	}
+	if (dL_dinput) {
+		// one launch writes every dim: the parts' gradients, zero where no nested encoding without parameters reads; the grids overwrite theirs
+		encoding_parts_backward(stream, parameterless_parts(c), n, n_input_dims, dL_denc, stride_k, stride_i, input, layout.in_stride_i, layout.in_stride_d, dL_dinput,
+		                        layout.dx_stride_i, layout.dx_stride_d);
+		for (size_t idx = 0; idx < c.nested.size(); ++idx) {
+			const EncodingDesc& e = c.nested[idx];
+			if (!e.is_grid()) continue;
+			if (idx >= ctx.nested_dy_dx.size() || !ctx.nested_dy_dx[idx].ptr) throw std::runtime_error("backward: dL_dinput requested but forward was not run with prepare_input_gradients");
+			GridIO io = {input + (size_t)e.dims_to_encode_begin * layout.in_stride_d, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
+			nested_grid_backward_input(stream, e.n_dims, e.n_output_dims, io, dL_denc + (size_t)e.output_row * stride_k, (const float*)ctx.nested_dy_dx[idx].ptr,
+			                           dL_dinput + (size_t)e.dims_to_encode_begin * layout.dx_stride_d, layout.dx_stride_i, layout.dx_stride_d);
+		}
+	}
+	return dL_denc;
+}
+
 // Encoding forward into a feature-major (SoA) or sample-major (AoS) half matrix.
 void encoding_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const half_t* enc_params, half_t* out,
-                             bool soa, float* dy_dx) {
+                             bool soa, float* dy_dx, ForwardCtx* ctx, bool prepare_input_gradients) {
 	const EncodingDesc& e = md.enc;
 	const uint32_t stride_k = soa ? n : 1u, stride_i = soa ? 1u : e.padded_output_width;
 	ProfScope prof(profiler, stream, STAGE_GRID_FWD);
-	if (e.is_grid) {
+	if (e.is_composite()) {
+		composite_forward(stream, e, layout, n, input, enc_params, out, stride_k, stride_i, ctx, prepare_input_gradients);
+	} else if (e.is_grid()) {
 		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
 		grid_forward(stream, e.grid, io, enc_params, out, dy_dx);
 		const uint32_t n_to_pad = e.padded_output_width - e.n_output_dims;
@@ -76,18 +194,18 @@ void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, cons
 		ctx->n = n;
 	}
 	float* dy_dx = nullptr;
-	if (ctx && prepare_input_gradients && md.enc.is_grid) {
+	if (ctx && prepare_input_gradients && md.enc.is_grid()) {
 		ctx->dy_dx = Scratch(stream, (size_t)md.enc.n_output_dims * n * md.n_input_dims * sizeof(float));
 		dy_dx = ctx->dy_dx.as<float>();
 	}
 	if (!md.has_network) {
-		encoding_forward(stream, profiler, md, layout, n, input, params, output, /*soa=*/false, dy_dx);
+		encoding_forward(stream, profiler, md, layout, n, input, params, output, /*soa=*/false, dy_dx, ctx, prepare_input_gradients);
 		return;
 	}
 	// inference into the caller's fp32 matrix with an Identity encoding that pads nothing: the inference kernel reads the fp32 input itself
 	// (MlpF32Input; no encoding kernel, no encoded matrix)
 	const EncodingDesc& e = md.enc;
-	if (!ctx && !e.is_grid && !e.is_frequency && !e.is_oneblob && e.n_dims == e.padded_output_width && layout.in_stride_i == e.n_dims && layout.in_stride_d == 1u &&
+	if (!ctx && e.kind == EncodingKind::Identity && e.n_dims == e.padded_output_width && layout.in_stride_i == e.n_dims && layout.in_stride_d == 1u &&
 	    ((uintptr_t)input & 15u) == 0u && g_fused_identity_input.load() != 0 && mlp_infer_f32_input_supported(md.net.mlp, n)) {
 		MlpF32Input f32_input;
 		f32_input.x = input;
@@ -101,7 +219,7 @@ void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, cons
 	Scratch enc_local;
 	Scratch& enc = ctx ? ctx->enc : enc_local;
 	enc = Scratch(stream, (size_t)md.enc.padded_output_width * n * sizeof(half_t));
-	encoding_forward(stream, profiler, md, layout, n, input, params + md.n_mlp_params(), enc.as<half_t>(), /*soa=*/true, dy_dx);
+	encoding_forward(stream, profiler, md, layout, n, input, params + md.n_mlp_params(), enc.as<half_t>(), /*soa=*/true, dy_dx, ctx, prepare_input_gradients);
 	half_t* hidden = nullptr;
 	if (ctx && !backward_recomputes(md)) {
 		ctx->hidden = Scratch(stream, (size_t)md.net.n_hidden_layers * n * md.net.mlp.width * sizeof(half_t));
@@ -132,7 +250,11 @@ void inference_to_f32(hipStream_t stream, const Model& md, const IoLayout& layou
 uint32_t widest_matrix(const Model& md) {
 	uint32_t w = std::max(md.enc.padded_output_width, md.n_input_dims);
 	if (md.has_network) w = std::max(w, std::max(md.net.mlp.width * md.net.n_hidden_layers, md.net.mlp.padded_out));
-	if (md.enc.is_grid) w = std::max(w, md.enc.n_output_dims * md.n_input_dims);  // dy_dx
+	if (md.enc.is_grid()) w = std::max(w, md.enc.n_output_dims * md.n_input_dims);  // dy_dx
+	w = std::max(w, md.enc.unreduced_width());  // a Composite's Sum / Product
+	for (const EncodingDesc& e : md.enc.nested) {
+		if (e.is_grid()) w = std::max(w, e.n_output_dims * e.n_dims);  // a nested grid's dy_dx
+	}
 	return w;
 }
 
@@ -253,7 +375,34 @@ void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, 
                               uint32_t stride_k, uint32_t stride_i, half_t* dL_dparams, bool want_grads, bool accumulate, const float* input,
                               uint32_t lds_level_budget, const LevelGroups* groups) {
 	const EncodingDesc& e = md.enc;
-	if (e.is_grid) {
+	if (e.is_composite()) {
+		Scratch dL_dunreduced;
+		dL_denc = composite_backward_input(stream, e, layout, ctx, n, md.n_input_dims, dL_dinput, dL_denc, stride_k, stride_i, input, dL_dunreduced);
+		if (want_grads && e.n_params > 0) {
+			// every nested grid on its own slice of dL_dy, its gradients at its own parameter offset: Overwrite / Accumulate hold per slice, the
+			// bucketed backward's workspace is requested per grid (the plain path: no level groups)
+			const GridBackwardMode mode = (GridBackwardMode)g_grid_backward_mode.load();
+			if (lds_level_budget == 0) lds_level_budget = g_default_lds_slice_bytes;
+			PhaseTimer timer = {profiler, stream, /*counts=*/true};
+			for (const EncodingDesc& g : e.nested) {
+				if (!g.is_grid() || g.n_params == 0) continue;
+				GridIO io = {input + (size_t)g.dims_to_encode_begin * layout.in_stride_d, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
+				GridBackwardWorkspace ws = grid_backward_workspace_size(g.grid, n, mode, lds_level_budget);
+				Scratch queues;
+				if (ws.scratch_bytes) {
+					queues = Scratch(stream, ws.scratch_bytes);
+					ws.scratch = queues.ptr;
+					ws.scratch_bytes = queues.bytes;
+					ws.counters = ZeroedCounters::get(stream, ws.n_counters);
+				}
+				ws.phase_hook = grid_backward_phase_hook;
+				ws.hook_user = &timer;
+				grid_backward(stream, g.grid, io, dL_denc + (size_t)g.output_row * stride_k, dL_dparams + md.n_mlp_params() + g.param_offset, accumulate, mode, lds_level_budget, ws);
+				timer.counts = false;  // one backward pass per step, however many grids it has
+			}
+			if (groups && groups->ready) groups->ready(groups->ctx, md.n_mlp_params(), md.n_params());
+		}
+	} else if (e.is_grid()) {
 		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
 		if (want_grads && e.n_params > 0) {
 			half_t* grid_grads = dL_dparams + md.n_mlp_params();
@@ -322,7 +471,9 @@ void encoding_forward_f32(hipStream_t stream, const Model& md, const IoLayout& l
 		ctx->n = n;
 	}
 	const uint32_t stride_k = 1u, stride_i = e.padded_output_width;
-	if (e.is_grid) {
+	if (e.is_composite()) {
+		composite_forward(stream, e, layout, n, input, params, out, stride_k, stride_i, ctx, prepare_input_gradients);
+	} else if (e.is_grid()) {
 		float* dy_dx = nullptr;
 		if (ctx && prepare_input_gradients) {
 			ctx->dy_dx = Scratch(stream, (size_t)e.n_output_dims * n * md.n_input_dims * sizeof(float));
@@ -342,8 +493,16 @@ void encoding_backward_f32(hipStream_t stream, const Model& md, const IoLayout& 
 	if (n == 0) return;
 	if (ctx.n != n) throw std::runtime_error("backward: batch size does not match the forward context");
 	const EncodingDesc& e = md.enc;
-	const uint32_t stride_k = 1u, stride_i = e.padded_output_width;
-	if (e.is_grid) {
+	uint32_t stride_k = 1u, stride_i = e.padded_output_width;
+	if (e.is_composite()) {
+		Scratch dL_dunreduced;
+		const float* dL_denc = composite_backward_input(stream, e, layout, ctx, n, md.n_input_dims, dL_dinput, dL_doutput, stride_k, stride_i, input, dL_dunreduced);
+		for (const EncodingDesc& g : e.nested) {
+			if (!dL_dparams || !g.is_grid() || g.n_params == 0) continue;
+			GridIO io = {input + (size_t)g.dims_to_encode_begin * layout.in_stride_d, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
+			grid_backward_f32(stream, g.grid, io, dL_denc + (size_t)g.output_row * stride_k, dL_dparams + g.param_offset, /*accumulate=*/false);
+		}
+	} else if (e.is_grid()) {
 		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
 		if (dL_dparams && e.n_params > 0) grid_backward_f32(stream, e.grid, io, dL_doutput, dL_dparams, /*accumulate=*/false);  // GradientMode::Overwrite, cpp_api.cu:115
 		if (dL_dinput) {

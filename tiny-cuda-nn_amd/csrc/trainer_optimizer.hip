@@ -117,7 +117,7 @@ using namespace tcnn_hip;
 // TCNN_ADAM_STEP_DEFICITS=1 (=0: counters, =2: bytes).
 static int choose_step_representation(const tcnn_trainable_model* tm) {
 	const int deficits = ADAM_STEPS_DEFICITS8;
-	if (!tm->md.enc.is_grid) return deficits;  // network weights are stepped every time
+	if (!tm->md.enc.is_grid()) return deficits;  // network weights are stepped every time
 	const auto& g = tm->md.enc.grid;
 	uint32_t largest = 0;
 	for (uint32_t l = 0; l < g.n_levels; ++l) largest = std::max(largest, g.offset[l + 1] - g.offset[l]);

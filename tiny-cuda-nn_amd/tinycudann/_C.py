@@ -119,6 +119,8 @@ _sig("tcnn_module_set_jit_fusion", _i, _vp, _i)
 _sig("tcnn_module_grid_indices", _i, _vp, _vp, _u32, _vp, _vp)
 _sig("tcnn_module_grid_level_n_params", _i, _vp, _u32, C.POINTER(_sz))
 _sig("tcnn_module_grid_level_params_offset", _i, _vp, _u32, C.POINTER(_sz))
+_sig("tcnn_module_n_nested", _u32, _vp)
+_sig("tcnn_module_nested_layout", _i, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz))
 _sig("tcnn_create_from_config", _i, _u32, _u32, _cp, _u32, C.POINTER(_vp))
 _sig("tcnn_trainable_model_destroy", None, _vp)
 _sig("tcnn_trainer_training_step", _i, _vp, _vp, _u32, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, C.POINTER(_vp))
@@ -538,6 +540,17 @@ class Module:
         _check(_lib.tcnn_module_grid_level_params_offset(self._h, level, C.byref(v)))
         return v.value
 
+    def nested_layout(self):
+        """The nested encodings of a Composite, in order (empty for every other module): where each reads its input dims, writes its rows of the
+        (unreduced) encoded matrix and keeps its parameters."""
+        out = []
+        for i in range(int(_lib.tcnn_module_n_nested(self._h))):
+            layout, params = (C.c_uint32 * 4)(), (C.c_size_t * 2)()
+            _check(_lib.tcnn_module_nested_layout(self._h, i, layout, params))
+            out.append({"dims_to_encode_begin": layout[0], "n_dims_to_encode": layout[1], "output_row": layout[2], "padded_output_width": layout[3],
+                        "params_offset": params[0], "n_params": params[1]})
+        return out
+
 
 class Pcg32:
     """`default_rng_t rng{seed}` + generate_random_uniform (random.h:39-75): a position in the pcg32 stream of `seed`."""
@@ -597,6 +610,7 @@ class ExtModule:
     grid_indices = Module.grid_indices
     grid_level_n_params = Module.grid_level_n_params
     grid_level_params_offset = Module.grid_level_params_offset
+    nested_layout = Module.nested_layout
 
 
 def ext_apply(module, x, params, loss_scale):
