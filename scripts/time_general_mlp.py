@@ -3,7 +3,10 @@ inference, the whole training step, and the network's share of the step (the tra
 and, for comparison, the 128 x 2 / 128 x 4 networks on the three-pass route of the fused widths (tcnn_set_fused_network_passes(0):
 forward with saved activations -> loss -> backward), per FLOP.  HIP events, warm-up, then --steps timed steps.
 
-usage: python scripts/time_general_mlp.py [--steps 200] [--warmup 20] [--n 262144] [--out results.json]"""
+--activation Sine / SiLU times the same networks with a hidden activation that keeps its pre-activations (accurate sinf / cosf, a second
+16-bit store per hidden layer; every width then runs layer by layer); --shapes picks a subset, e.g. 256x2.
+
+usage: python scripts/time_general_mlp.py [--steps 200] [--warmup 20] [--n 262144] [--activation ReLU] [--shapes 256x2,256x4,128x2,128x4] [--out results.json]"""
 import argparse
 import json
 import os
@@ -27,6 +30,8 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--n", type=int, default=1 << 18)
+    ap.add_argument("--activation", default="ReLU", help="hidden activation of the timed networks")
+    ap.add_argument("--shapes", default="256x2,256x4,128x2,128x4", help="comma-separated WIDTHxHIDDEN_LAYERS out of the four")
     ap.add_argument("--out", default=None, help="also write the results to this JSON file")
     args = ap.parse_args()
     import numpy as np
@@ -54,12 +59,16 @@ def main():
         return a.elapsed_time(b) / args.steps
 
     results = []
+    keeps_pre = args.activation.lower() in ("sine", "silu")
+    wanted = set(args.shapes.split(","))
     for width, hidden, fused_passes in ((256, 2, 1), (256, 4, 1), (128, 2, 0), (128, 4, 0)):
+        if f"{width}x{hidden}" not in wanted:
+            continue
         T._C.set_fused_network_passes(bool(fused_passes))
         try:
             cfg = {"loss": {"otype": "RelativeL2"},
                    "optimizer": {"otype": "Adam", "learning_rate": 1e-2, "beta1": 0.9, "beta2": 0.99, "epsilon": 1e-15, "l2_reg": 1e-6},
-                   "encoding": enc, "network": {"otype": "MLP", "activation": "ReLU", "output_activation": "None", "n_neurons": width, "n_hidden_layers": hidden}}
+                   "encoding": enc, "network": {"otype": "MLP", "activation": args.activation, "output_activation": "None", "n_neurons": width, "n_hidden_layers": hidden}}
             tm = T.create_from_config(3, 4, cfg, seed=1337)
             step_ms = timed(lambda: tm.training_step(x, t, want_context=False))
             infer_ms = timed(lambda: tm.inference(x))
@@ -73,16 +82,17 @@ def main():
         fwd_flop, train_flop = network_flops(n, 32, width, hidden)
         mlp_ms = stages.get("mlp_forward", 0.0) + stages.get("mlp_backward", 0.0) + stages.get("mlp_train_fused", 0.0)
         n_params = width * 32 + (hidden - 1) * width * width + 16 * width
-        r = {"network": f"{width}x{hidden}", "route": "layer-by-layer" if width == 256 else "fused kernels, three passes", "n": n,
+        general = width == 256 or keeps_pre
+        r = {"network": f"{width}x{hidden}", "activation": args.activation, "route": "layer-by-layer" if general else "fused kernels, three passes", "n": n,
              "training_step_ms": round(step_ms, 4), "inference_ms": round(infer_ms, 4),
              "stage_ms": {k: round(v, 4) for k, v in stages.items()},
              "network_train_ms": round(mlp_ms, 4), "network_train_gflop": round(train_flop / 1e9, 2),
              "network_train_tflops": round(train_flop / (mlp_ms * 1e-3) / 1e12, 1) if mlp_ms else None,
              "fraction_of_mfma_roof": round(train_flop / (mlp_ms * 1e-3) / PEAK_FP16_MFMA, 4) if mlp_ms else None,
              "ns_per_gflop_training": round(mlp_ms * 1e6 / (train_flop / 1e9), 1) if mlp_ms else None,
-             "saved_activations_mb": round(hidden * n * width * 2 / 2 ** 20, 1),
-             "backward_workspace_mb": round(hidden * n * width * 2 / 2 ** 20, 1) if width == 256 else 0.0,
-             "inference_ping_pong_mb": round(2 * n * width * 2 / 2 ** 20, 1) if width == 256 else 0.0,
+             "saved_activations_mb": round((2 if keeps_pre else 1) * hidden * n * width * 2 / 2 ** 20, 1),
+             "backward_workspace_mb": round(hidden * n * width * 2 / 2 ** 20, 1) if general else 0.0,
+             "inference_ping_pong_mb": round(2 * n * width * 2 / 2 ** 20, 1) if general else 0.0,
              "n_mlp_params": n_params}
         results.append(r)
         print(json.dumps(r), flush=True)

@@ -1,6 +1,9 @@
 // activation_device.h -- the activations FullyFusedMLP offers for its hidden layers (fully_fused_mlp.cu:690-697) and,
 // together with None, for the output layer; reference arithmetic: common_device.h:108-186 (forward) and :363-418
-// (backward, expressed through the POST-activation value -- which is all that is stored).
+// (backward, expressed through the POST-activation value -- which is all that the fused kernels store).
+// SiLU and Sine (common_device.h:131-152 forward, :253-277 backward) have a derivative that needs the PRE-activation: only the
+// layer-by-layer network (mlp_general.hip) offers them, as hidden activations, through act_forward4_pre / act_backward4_pre below and a saved
+// stack with a second block (mlp_kernels.h mlp_saved_activation_bytes).  No other function of this file is entered with them.
 #pragma once
 #include "tcnn_device.h"
 #if defined(TCNN_HOST_EMU)
@@ -9,7 +12,7 @@
 
 namespace tcnn_hip {
 
-enum class Activation : int { None = 0, ReLU = 1, LeakyReLU = 2, Exponential = 3, Sigmoid = 4, Squareplus = 5, Softplus = 6, Tanh = 7 };
+enum class Activation : int { None = 0, ReLU = 1, LeakyReLU = 2, Exponential = 3, Sigmoid = 4, Squareplus = 5, Softplus = 6, Tanh = 7, SiLU = 8, Sine = 9 };  // 0-7: the oracle's ORC_ACT_* numbering
 constexpr float K_ACT = 10.0f;  // common_device.h:108
 
 // The fused kernels evaluate activations at dozens of unrolled sites: ReLU / None stay inline, everything else is ONE
@@ -48,6 +51,8 @@ TCNN_DEVICE float act_forward(uint32_t act, float x) {
 	return x;
 }
 TCNN_HOST_DEVICE bool act_is_simple(uint32_t act) { return act == (uint32_t)Activation::ReLU || act == (uint32_t)Activation::None; }
+// the derivative cannot be written through the post-activation value (sin is not monotonic; x * logistic(x) neither)
+TCNN_HOST_DEVICE bool act_needs_preactivation(uint32_t act) { return act == (uint32_t)Activation::SiLU || act == (uint32_t)Activation::Sine; }
 
 // dL/d(pre-activation) = v * f'(x) with f' written in terms of the stored fp16 post-activation value; the factor is
 // rounded to fp16 like the reference's (T)(...) before the multiply.  ReLU keeps the select form (exact, no -0).
@@ -177,6 +182,55 @@ TCNN_DEVICE h4 act_backward4(uint32_t act, f4 v, h4 forward_value) {
 #pragma unroll
 	for (uint32_t j = 0; j < 4; ++j) v[j] = (relu && !(forward_value[j] > (half_t)0.0f)) ? 0.0f : v[j];
 	return h4{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+}
+
+// ---- SiLU / Sine: the activations that keep their pre-activation.  The arithmetic is the reference's two-pass form (a product written as a
+// 16-bit matrix, then an element-wise pass over it): the accumulator is rounded to the 16-bit type FIRST, the activation is evaluated in fp32
+// on the rounded value and rounded once more; backward, the rounded accumulator is multiplied by the derivative at the saved pre-activation,
+// itself rounded -- a 16-bit x 16-bit product with one rounding (exact in fp32 before it: 11 + 11 or 8 + 8 significant bits).
+// The accurate sinf / cosf, not the hardware's v_sin_f32 / v_cos_f32: the first layer of a SIREN network has pre-activations of tens of
+// radians, where the fast forms lose digits (their argument reduction is a multiply by 1 / 2 pi in fp32).  Same shape as the functions above:
+// ONE out-of-line body per kernel, entered once per fragment, mfma_settle in front of the branch into it.
+TCNN_DEVICE_NOINLINE f4 act_forward4_pre_general(uint32_t act, f4 x) {
+	f4 y;
+	if (act == (uint32_t)Activation::Sine) {
+#pragma unroll
+		for (uint32_t j = 0; j < 4; ++j) y[j] = sinf(x[j]);
+	} else {  // SiLU
+#pragma unroll
+		for (uint32_t j = 0; j < 4; ++j) y[j] = x[j] * (1.0f / (1.0f + expf(-x[j])));
+	}
+	return y;
+}
+// accumulator fragment -> `pre` (what a training pass saves) and the activation of `pre`
+TCNN_DEVICE h4 act_forward4_pre(uint32_t act, f4 x, h4& pre) {
+	mfma_settle(x);
+	pre = h4{(half_t)x[0], (half_t)x[1], (half_t)x[2], (half_t)x[3]};
+	const f4 y = act_forward4_pre_general(act, f4{(float)pre[0], (float)pre[1], (float)pre[2], (float)pre[3]});
+	return h4{(half_t)y[0], (half_t)y[1], (half_t)y[2], (half_t)y[3]};
+}
+TCNN_DEVICE_NOINLINE f4 act_derivative4_pre_general(uint32_t act, h4 pre) {
+	f4 d;
+	if (act == (uint32_t)Activation::Sine) {
+#pragma unroll
+		for (uint32_t j = 0; j < 4; ++j) d[j] = cosf((float)pre[j]);
+	} else {  // SiLU
+#pragma unroll
+		for (uint32_t j = 0; j < 4; ++j) {
+			const float x = (float)pre[j], l = 1.0f / (1.0f + expf(-x));
+			d[j] = l + x * (l * (1.0f - l));
+		}
+	}
+	return d;
+}
+// (T)((float)(T)v * (float)(T)f'(pre)).  NOT act_backward4's form, which multiplies the fp32 accumulator.
+TCNN_DEVICE h4 act_backward4_pre(uint32_t act, f4 v, h4 pre) {
+	mfma_settle(v);
+	const f4 d = act_derivative4_pre_general(act, pre);
+	h4 out;
+#pragma unroll
+	for (uint32_t j = 0; j < 4; ++j) out[j] = (half_t)((float)(half_t)v[j] * (float)(half_t)d[j]);
+	return out;
 }
 
 template <bool GENERAL>

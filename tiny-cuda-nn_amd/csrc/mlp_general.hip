@@ -1,5 +1,6 @@
-// mlp_general.hip -- the layer-by-layer network for hidden widths the fused kernels are not built for: any multiple of 16 up to
-// MLP_GENERAL_MAX_WIDTH that is not 16 / 32 / 64 / 128.  Stands where the reference's CutlassMLP stands (cutlass_mlp.cu:110-330: one GEMM
+// mlp_general.hip -- the layer-by-layer network for what the fused kernels are not built for (mlp_kernels.h mlp_layer_by_layer): hidden
+// widths that are a multiple of 16 up to MLP_GENERAL_MAX_WIDTH other than 16 / 32 / 64 / 128, and -- at every width -- the hidden
+// activations whose derivative needs the pre-activation (SiLU, Sine).  Stands where the reference's CutlassMLP stands (cutlass_mlp.cu:110-330: one GEMM
 // with an activation epilogue per layer, one GEMM per layer for dL/d(pre-activation), one split-K GEMM per weight matrix) -- its BEHAVIOUR,
 // not its tiling.  Same parameter layout, transposed scratch and boundary layouts as the fused kernels (mlp_kernels.h), so everything
 // above the launchers is shared.
@@ -7,7 +8,9 @@
 // Two kernels:
 //   * k_mlp_general_layer:  Y[sample][m] = epilogue(sum_k Wm[m][k] X[sample][k]) for one matrix Wm [M][K] row-major.  Forward: Wm = a
 //     layer's weights, epilogue = activation.  Backward: Wm = the TRANSPOSED weights (params_t), X = dL/d(pre-activation) of the layer
-//     above, epilogue = the activation's derivative on the saved post-activation values.  Both operands have k contiguous, so the
+//     above, epilogue = the activation's derivative on the saved post-activation values.  SiLU / Sine (the _PRE epilogues): forward rounds
+//     the accumulator to 16 bits, stores it into the stack's second block (training) and applies the activation to the rounded value;
+//     backward multiplies the rounded accumulator by the rounded derivative at that saved pre-activation.  Both operands have k contiguous, so the
 //     weights are the MFMA A operand and the activations the B operand straight out of [row][k] LDS tiles, and the accumulator fragment
 //     (4 consecutive m for one sample) is an 8-byte store into the sample-major result.
 //     Workgroup: 4 waves, tile = (16 * NMB m) x (128 samples); wave w owns samples 32w .. 32w+31 and all NMB blocks of m
@@ -41,7 +44,8 @@ constexpr uint32_t GEN_BK = 64;            // k per LDS stage
 constexpr uint32_t GEN_LDK = GEN_BK + 8;   // row stride (halves) of the [row][k] stages
 constexpr uint32_t GEN_MAX_MB = 4;         // blocks of 16 m per workgroup tile, at most
 
-enum : uint32_t { GEN_EPI_NONE = 0, GEN_EPI_FORWARD = 1, GEN_EPI_BACKWARD = 2 };
+// _PRE: the epilogues of the activations that keep their pre-activation (SiLU / Sine, activation_device.h act_forward4_pre / act_backward4_pre)
+enum : uint32_t { GEN_EPI_NONE = 0, GEN_EPI_FORWARD = 1, GEN_EPI_BACKWARD = 2, GEN_EPI_FORWARD_PRE = 3, GEN_EPI_BACKWARD_PRE = 4 };
 
 struct GenLayerArgs {
 	uint32_t n, M, K;
@@ -51,8 +55,9 @@ struct GenLayerArgs {
 	half_t* Y;            // sample-major [n][ldy], or feature-major [M][n] (Y_FM)
 	uint32_t ldy;
 	const half_t* F;      // GEN_EPI_BACKWARD: the post-activation values the derivative is taken at, sample-major [n][ldf]
-	uint32_t ldf;
+	uint32_t ldf;         // GEN_EPI_BACKWARD_PRE: the PRE-activation values, same layout
 	uint32_t act;
+	half_t* P;            // GEN_EPI_FORWARD_PRE: where the rounded pre-activations go, sample-major [n][ldy]; null: not saved (inference)
 };
 
 template <uint32_t NMB, uint32_t EPI, bool X_FM, bool Y_FM, bool GENERAL>
@@ -171,6 +176,15 @@ __global__ void __launch_bounds__(GEN_THREADS) k_mlp_general_layer(const GenLaye
 			} else if constexpr (EPI == GEN_EPI_BACKWARD) {
 				const h4 fv = *(const h4*)(a.F + sample * a.ldf + m);
 				o = act_backward4<GENERAL>(a.act, acc[mb][sb], fv);
+			} else if constexpr (EPI == GEN_EPI_FORWARD_PRE) {
+				// one launch where the reference runs a product and an element-wise pass: the rounded accumulator is the saved
+				// pre-activation AND the activation's argument.  Both stores behind everything this iteration computes; it loads nothing.
+				h4 pre;
+				o = act_forward4_pre(a.act, acc[mb][sb], pre);
+				if (valid && a.P) *(h4*)(a.P + sample * a.ldy + m) = pre;
+			} else if constexpr (EPI == GEN_EPI_BACKWARD_PRE) {
+				const h4 pre = *(const h4*)(a.F + sample * a.ldf + m);
+				o = act_backward4_pre(a.act, acc[mb][sb], pre);
 			} else {
 				const f4 v = acc[mb][sb];
 				o = h4{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
@@ -336,8 +350,11 @@ static void gen_launch_layer(hipStream_t stream, const GenLayerArgs& a) {
 	const dim3 grid(div_round_up(a.M, 16u * nmb) * (a.n / GEN_BN)), block(GEN_THREADS);
 	const uint32_t lds_bytes = 2u * (16u * nmb + GEN_BN) * GEN_LDK * (uint32_t)sizeof(half_t);  // <= 54 KiB
 	const bool general = EPI != GEN_EPI_NONE && !act_is_simple(a.act);
+	// the _PRE epilogues have one instance per tile shape (GENERAL says nothing there); the other instances are what they were
 #define TCNN_GEN_LAUNCH(NMB_)                                                                                                 \
-	if (general) {                                                                                                            \
+	if constexpr (EPI == GEN_EPI_FORWARD_PRE || EPI == GEN_EPI_BACKWARD_PRE) {                                                \
+		TCNN_LAUNCH((k_mlp_general_layer<NMB_, EPI, X_FM, Y_FM, true>), grid, block, lds_bytes, stream, a);                   \
+	} else if (general) {                                                                                                     \
 		TCNN_LAUNCH((k_mlp_general_layer<NMB_, EPI, X_FM, Y_FM, EPI != GEN_EPI_NONE>), grid, block, lds_bytes, stream, a);    \
 	} else {                                                                                                                  \
 		TCNN_LAUNCH((k_mlp_general_layer<NMB_, EPI, X_FM, Y_FM, false>), grid, block, lds_bytes, stream, a);                  \
@@ -369,13 +386,22 @@ void mlp_general_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const
 		ping = ping_scratch.as<half_t>();
 	}
 #endif
+	// SiLU / Sine: the saved stack has a second block, the pre-activations (mlp_saved_activation_bytes); inference saves neither
+	const bool keeps_pre = act_needs_preactivation(m.activation);
+	half_t* pre_block = keeps_pre && hidden ? hidden + (HM + 1) * layer_elems : nullptr;
 	const half_t* Wl = params;
 	const half_t* x = input;
 	uint32_t K = m.in_width;
 	for (uint32_t layer = 0; layer <= HM; ++layer) {
 		half_t* y = hidden ? hidden + layer * layer_elems : ping + (layer & 1u) * layer_elems;
-		const GenLayerArgs a = {n, W, K, Wl, x, K, y, W, nullptr, 0u, m.activation};
-		if (layer == 0) {
+		const GenLayerArgs a = {n, W, K, Wl, x, K, y, W, nullptr, 0u, m.activation, pre_block ? pre_block + layer * layer_elems : nullptr};
+		if (keeps_pre) {
+			if (layer == 0) {
+				gen_launch_layer<GEN_EPI_FORWARD_PRE, true, false>(stream, a);
+			} else {
+				gen_launch_layer<GEN_EPI_FORWARD_PRE, false, false>(stream, a);
+			}
+		} else if (layer == 0) {
 			gen_launch_layer<GEN_EPI_FORWARD, true, false>(stream, a);  // the network input is feature-major
 		} else {
 			gen_launch_layer<GEN_EPI_FORWARD, false, false>(stream, a);
@@ -384,7 +410,7 @@ void mlp_general_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const
 		x = y;
 		K = W;
 	}
-	const GenLayerArgs a = {n, m.padded_out, W, Wl, x, W, output, m.padded_out, nullptr, 0u, m.output_activation};
+	const GenLayerArgs a = {n, m.padded_out, W, Wl, x, W, output, m.padded_out, nullptr, 0u, m.output_activation, nullptr};
 	gen_launch_layer<GEN_EPI_FORWARD, false, false>(stream, a);
 }
 
@@ -424,17 +450,23 @@ void mlp_general_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, cons
 	const half_t* wt_hid = wt_in + (size_t)IN * W;              // HM x [W][W]  (row = input neuron of the matrix)
 	const half_t* wt_out = wt_hid + (size_t)HM * W * W;         // [W][OUTP]
 
-	// dA_last = (dY W_out) * act'(A_last), then down the hidden matrices
-	{
-		const GenLayerArgs a = {n, W, OUTP, wt_out, dL_doutput, OUTP, dact + HM * layer_elems, W, hidden + HM * layer_elems, W, m.activation};
-		gen_launch_layer<GEN_EPI_BACKWARD, false, false>(stream, a);
-	}
+	// dA_last = (dY W_out) * act'(A_last), then down the hidden matrices.  The derivative is taken at the saved post-activations, or -- SiLU /
+	// Sine -- at the pre-activations in the stack's second block; the weight-gradient products below read the first block either way.
+	const bool keeps_pre = act_needs_preactivation(m.activation);
+	const half_t* at = keeps_pre ? hidden + (HM + 1) * layer_elems : hidden;
+	auto derivative_layer = [&](const GenLayerArgs& a) {
+		if (keeps_pre) {
+			gen_launch_layer<GEN_EPI_BACKWARD_PRE, false, false>(stream, a);
+		} else {
+			gen_launch_layer<GEN_EPI_BACKWARD, false, false>(stream, a);
+		}
+	};
+	derivative_layer({n, W, OUTP, wt_out, dL_doutput, OUTP, dact + HM * layer_elems, W, at + HM * layer_elems, W, m.activation, nullptr});
 	for (uint32_t j = HM; j-- > 0;) {
-		const GenLayerArgs a = {n, W, W, wt_hid + (size_t)j * W * W, dact + (j + 1) * layer_elems, W, dact + j * layer_elems, W, hidden + j * layer_elems, W, m.activation};
-		gen_launch_layer<GEN_EPI_BACKWARD, false, false>(stream, a);
+		derivative_layer({n, W, W, wt_hid + (size_t)j * W * W, dact + (j + 1) * layer_elems, W, dact + j * layer_elems, W, at + j * layer_elems, W, m.activation, nullptr});
 	}
 	if (dL_dinput) {  // no activation on the network input; feature-major like the input
-		const GenLayerArgs a = {n, IN, W, wt_in, dact, W, dL_dinput, 0u, nullptr, 0u, (uint32_t)Activation::None};
+		const GenLayerArgs a = {n, IN, W, wt_in, dact, W, dL_dinput, 0u, nullptr, 0u, (uint32_t)Activation::None, nullptr};
 		gen_launch_layer<GEN_EPI_NONE, false, true>(stream, a);
 	}
 	if (!partials) return;

@@ -1,7 +1,8 @@
 // mlp_kernels.h -- the MLP on gfx950 (16-bit storage, fp32 MFMA accumulation): fully fused kernels for 16/32/64/128 neurons, and a
 // layer-by-layer network (mlp_general.hip, the reference's CutlassMLP) for every other multiple of 16 up to MLP_GENERAL_MAX_WIDTH.
-// Both sit behind the same launchers (mlp_forward / mlp_backward / ...) with the same parameter and boundary layouts; what follows
-// describes the fused kernels.
+// Both sit behind the same launchers (mlp_forward / mlp_backward / ...) with the same parameter and boundary layouts; which of the two
+// a network takes is mlp_layer_by_layer(): a width outside 16/32/64/128, or -- at any width -- a hidden activation whose derivative needs
+// the pre-activation (SiLU, Sine), which the fused kernels do not keep.  What follows describes the fused kernels.
 //
 // Restates the BEHAVIOUR of reference src/fully_fused_mlp.cu:499-837 (kernel_mlp_fused,
 // kernel_mlp_fused_backward and the four CUTLASS call sites :786,:820,:829,:835) -- not its tiling.
@@ -21,7 +22,8 @@
 // Data layout at the kernel boundary:
 //   input / dL_dinput : half, feature-major  [in_width][n]   (the reference's SoA, grid.h:1070)
 //   output / dL_doutput: half, sample-major  [n][16]         (the reference's CM padded output)
-//   hidden (saved)    : half, [n_hidden][n][WIDTH] post-activation (fully_fused_mlp.cu:841-854)
+//   hidden (saved)    : half, [n_hidden][n][WIDTH] post-activation (fully_fused_mlp.cu:841-854); SiLU / Sine networks: followed by a
+//                       pre-activation block of the same shape (mlp_saved_activation_bytes)
 #pragma once
 #include "activation_device.h"
 #include "loss_device.h"
@@ -35,8 +37,8 @@ struct MlpMeta {
 	uint32_t width;             // 16 / 32 / 64 / 128 (fused kernels), or any other multiple of 16 <= MLP_GENERAL_MAX_WIDTH (layer by layer)
 	uint32_t padded_out;        // multiple of 16, <= MLP_MAX_OUT_WIDTH
 	uint32_t n_hidden_matmuls;  // n_hidden_layers - 1
-	uint32_t activation;        // Activation of the hidden layers
-	uint32_t output_activation; // Activation of the output layer (default None)
+	uint32_t activation;        // Activation of the hidden layers (SiLU / Sine: layer by layer at every width)
+	uint32_t output_activation; // Activation of the output layer (default None; never SiLU / Sine)
 	TCNN_HOST_DEVICE uint32_t n_params() const { return width * in_width + n_hidden_matmuls * width * width + padded_out * width; }
 };
 
@@ -84,10 +86,18 @@ constexpr uint32_t MLP_MAX_OUT_WIDTH = 128;  // padded; more than 16 outputs tra
 // the layer-by-layer network of the other widths (mlp_general.hip)
 constexpr uint32_t MLP_GENERAL_MAX_WIDTH = 1024;
 constexpr uint32_t MLP_GENERAL_MAX_IN_WIDTH = 1024;
-// the widths the fused kernels are instantiated for; every other one takes the layer-by-layer path
+// the widths the fused kernels are instantiated for
 TCNN_HOST_DEVICE bool mlp_fused_width(uint32_t width) { return width == 16u || width == 32u || width == 64u || width == 128u; }
+// THE place that decides the path: true -> mlp_general.hip, and every fused kernel's *_supported predicate is false
+TCNN_HOST_DEVICE bool mlp_layer_by_layer(const MlpMeta& m) { return !mlp_fused_width(m.width) || act_needs_preactivation(m.activation); }
+// The stack a forward pass with `hidden != nullptr` writes and the backward pass reads: [n_hidden][n][W] post-activations; for an activation
+// that needs them, followed by [n_hidden][n][W] pre-activations.  Readers of post-activations (the next layer, the weight-gradient
+// products) address the first block either way.
+TCNN_HOST_DEVICE size_t mlp_saved_activation_bytes(const MlpMeta& m, uint32_t n) {
+	return (size_t)(act_needs_preactivation(m.activation) ? 2u : 1u) * (m.n_hidden_matmuls + 1u) * n * m.width * sizeof(half_t);
+}
 
-// Forward.  hidden == nullptr -> inference (nothing saved).
+// Forward.  hidden == nullptr -> inference (nothing saved); otherwise mlp_saved_activation_bytes(m, n) bytes.
 void mlp_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, half_t* hidden,
                  half_t* output);
 
@@ -106,7 +116,7 @@ void mlp_output_activation_backward(hipStream_t stream, const MlpMeta& m, uint32
 // Backward.  dL_doutput is the gradient w.r.t. the output layer's PRE-activation (== dL/doutput when the output
 // activation is None).  params_t from mlp_transpose_weights.  dL_dinput may be null.  partials: fp32
 // [mlp_backward_n_partials][n_params] or null (GradientMode::Ignore).
-// Networks with more than MLP_MAX_HIDDEN_MATMULS_TRAIN + 1 hidden layers, and every network of a width outside 16/32/64/128, run a
+// Networks with more than MLP_MAX_HIDDEN_MATMULS_TRAIN + 1 hidden layers, and every mlp_layer_by_layer() network, run a
 // layer-by-layer formulation that needs `workspace` (mlp_backward_workspace_bytes, 0 for the others).
 size_t mlp_backward_workspace_bytes(const MlpMeta& m, uint32_t n);
 void mlp_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params_t, const half_t* input, const half_t* hidden,
@@ -184,10 +194,10 @@ SlabOrder mlp_train(hipStream_t stream, const MlpMeta& m, uint32_t n, const half
 void mlp_finalize_gradients(hipStream_t stream, const MlpMeta& m, uint32_t n_partials, const float* partials, half_t* grads, bool accumulate,
                             SlabOrder order = SlabOrder::Params);
 
-// ---- widths outside 16/32/64/128 (mlp_general.hip): one launch per layer and direction, one per weight matrix.  mlp_forward /
-// mlp_backward / mlp_backward_n_partials / mlp_backward_workspace_bytes route here by width; same contracts.  With hidden == nullptr the
+// ---- mlp_layer_by_layer() networks (mlp_general.hip): one launch per layer and direction, one per weight matrix.  mlp_forward /
+// mlp_backward / mlp_backward_n_partials / mlp_backward_workspace_bytes route here by that predicate; same contracts.  With hidden == nullptr the
 // forward pass keeps two ping-pong activation matrices in stream-ordered scratch of its own.  No fused training pass: mlp_train_supported
-// is false for these widths, so a training step is forward (saved activations) -> loss -> backward.
+// is false for them, so a training step is forward (saved activations) -> loss -> backward.
 void mlp_general_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, half_t* hidden, half_t* output);
 uint32_t mlp_general_n_partials(const MlpMeta& m, uint32_t n);
 size_t mlp_general_backward_workspace_bytes(const MlpMeta& m, uint32_t n);

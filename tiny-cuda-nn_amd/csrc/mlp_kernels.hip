@@ -995,7 +995,10 @@ __global__ void __launch_bounds__(32 * FINALIZE_GROUPS) k_mlp_finalize_gradients
 // host launchers
 // =============================================================================================
 static void check_meta(const MlpMeta& m, uint32_t n) {
-	const bool fused = mlp_fused_width(m.width);
+	const bool fused = !mlp_layer_by_layer(m);
+	if (act_needs_preactivation(m.output_activation)) {
+		throw std::runtime_error("MLP: SiLU / Sine cannot be the output activation (output activations must be expressible from the output value).");
+	}
 	if (!fused && (m.width < 16 || m.width > MLP_GENERAL_MAX_WIDTH || m.width % 16 != 0)) {
 		throw std::runtime_error("MLP: the number of neurons must be a multiple of 16 between 16 and " + std::to_string(MLP_GENERAL_MAX_WIDTH) + ", but got " +
 		                         std::to_string(m.width) + ".");
@@ -1033,7 +1036,7 @@ static void launch_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, con
 void mlp_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, half_t* hidden, half_t* output) {
 	check_meta(m, n);
 	if (n == 0) return;
-	if (!mlp_fused_width(m.width)) {
+	if (mlp_layer_by_layer(m)) {
 		mlp_general_forward(stream, m, n, params, input, hidden, output);
 		return;
 	}
@@ -1054,7 +1057,7 @@ void mlp_transpose_weights(hipStream_t stream, const MlpMeta& m, const half_t* p
 }
 
 uint32_t mlp_backward_n_partials(const MlpMeta& m, uint32_t n) {
-	if (!mlp_fused_width(m.width)) return mlp_general_n_partials(m, n);
+	if (mlp_layer_by_layer(m)) return mlp_general_n_partials(m, n);
 	const uint32_t n_tiles = n / MLP_BWD_TILE;
 #ifndef TCNN_MLP_PARTIALS
 #define TCNN_MLP_PARTIALS 512
@@ -1127,7 +1130,7 @@ static void dispatch_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, 
 }
 
 size_t mlp_backward_workspace_bytes(const MlpMeta& m, uint32_t n) {
-	if (!mlp_fused_width(m.width)) return mlp_general_backward_workspace_bytes(m, n);
+	if (mlp_layer_by_layer(m)) return mlp_general_backward_workspace_bytes(m, n);
 	const bool layer_by_layer = m.n_hidden_matmuls > MLP_MAX_HIDDEN_MATMULS_TRAIN || m.padded_out != 16;
 	return layer_by_layer ? (size_t)(m.n_hidden_matmuls + 1) * n * m.width * sizeof(half_t) : 0;
 }
@@ -1136,7 +1139,7 @@ void mlp_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t
                   const half_t* dL_doutput, half_t* dL_dinput, float* partials, void* workspace) {
 	check_meta(m, n);
 	if (n == 0) return;
-	if (!mlp_fused_width(m.width)) {
+	if (mlp_layer_by_layer(m)) {
 		mlp_general_backward(stream, m, n, params_t, input, hidden, dL_doutput, dL_dinput, partials, workspace);
 		return;
 	}
@@ -1189,7 +1192,7 @@ uint32_t mlp_train_n_partials(const MlpMeta& m, uint32_t n, LossType loss) {
 }
 
 bool mlp_train_supported(const MlpMeta& m) {
-	if (!mlp_fused_width(m.width)) return false;  // the layer-by-layer widths: forward with saved activations -> loss -> backward
+	if (mlp_layer_by_layer(m)) return false;  // the layer-by-layer networks: forward with saved activations -> loss -> backward
 	// 128-wide networks: k_mlp_train measured no faster than the three-kernel path (the weight-gradient accumulators of four
 	// 128 x 128 matrices spill at 64-sample tiles); they have their own kernel (mlp_train_wide.hip) for 32 / 64 inputs
 	if (m.width == 128) return mlp_train_wide_supported(m, MLP_BWD_TILE);

@@ -764,7 +764,7 @@ __global__ void __launch_bounds__(MLP_WAVE_THREADS) k_mlp_infer_wave(const MlpMe
 
 // ---- the register-resident wave-per-strip variant: instantiated for the shapes whose operands fit one wave's registers
 bool mlp_train_wave_supported(const MlpMeta& m, uint32_t n, LossType loss) {
-	if (m.padded_out != 16 || (m.in_width != 32 && m.in_width != 64)) return false;
+	if (mlp_layer_by_layer(m) || m.padded_out != 16 || (m.in_width != 32 && m.in_width != 64)) return false;
 	// ReLU / None and (Relative)L2 only: the instances with out-of-line activation / loss calls gain nothing here
 	if (!act_is_simple(m.activation) || !act_is_simple(m.output_activation) || !loss_is_simple(loss)) return false;
 	if (n > (1u << 26)) return false;  // 32-bit element offsets inside the kernel
@@ -841,7 +841,7 @@ void mlp_train_wave(hipStream_t stream, const MlpMeta& m, uint32_t n, const half
 
 // ---- inference instances
 bool mlp_infer_wave_supported(const MlpMeta& m, uint32_t n) {
-	if (m.padded_out != 16 || (m.in_width != 32 && m.in_width != 64) || n > (1u << 25)) return false;
+	if (mlp_layer_by_layer(m) || m.padded_out != 16 || (m.in_width != 32 && m.in_width != 64) || n > (1u << 25)) return false;
 	if (!act_is_simple(m.activation) || !act_is_simple(m.output_activation)) return false;
 	return (m.width == 64 && m.n_hidden_matmuls <= 2) || (m.width == 32 && m.n_hidden_matmuls <= 3 && m.in_width == 32);
 }

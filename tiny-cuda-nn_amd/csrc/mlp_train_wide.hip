@@ -328,7 +328,7 @@ static uint32_t mlp_train_wide_lds_bytes(const MlpMeta& m) {
 }
 
 bool mlp_train_wide_supported(const MlpMeta& m, uint32_t n) {
-	return m.width == WIDE && m.padded_out == 16 && (m.in_width == 32 || m.in_width == 64) &&
+	return !mlp_layer_by_layer(m) && m.width == WIDE && m.padded_out == 16 && (m.in_width == 32 || m.in_width == 64) &&
 	       m.n_hidden_matmuls <= MLP_MAX_HIDDEN_MATMULS_TRAIN && n % WIDE_S == 0 && mlp_train_wide_lds_bytes(m) <= 160u * 1024u;
 }
 

@@ -22,7 +22,7 @@ static const char* to_string(GridType t) { return t == GridType::Hash ? "Hash" :
 static const char* to_string(InterpolationType t) {
 	return t == InterpolationType::Nearest ? "Nearest" : t == InterpolationType::Linear ? "Linear" : "Smoothstep";
 }
-static const char* const ACTIVATION_NAMES[] = {"None", "ReLU", "LeakyReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus", "Tanh"};
+static const char* const ACTIVATION_NAMES[] = {"None", "ReLU", "LeakyReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus", "Tanh", "SiLU", "Sine"};
 static const char* to_string(Activation a) { return ACTIVATION_NAMES[(int)a]; }
 
 static GridType string_to_grid_type(const std::string& s) {  // common_host.cu:112-122
@@ -38,12 +38,9 @@ static InterpolationType string_to_interpolation_type(const std::string& s) {  /
 	throw std::runtime_error("Invalid interpolation type: " + s);
 }
 static Activation string_to_activation(const std::string& s) {  // common_host.cu:70-96
-	for (int i = 0; i < 8; ++i) {
+	// (SiLU and Sine parse like the others; where they are allowed is create_network_desc's business)
+	for (size_t i = 0; i < sizeof(ACTIVATION_NAMES) / sizeof(ACTIVATION_NAMES[0]); ++i) {
 		if (equals_case_insensitive(s, ACTIVATION_NAMES[i])) return (Activation)i;
-	}
-	// SiLU and Sine need stored pre-activations, which FullyFusedMLP does not keep (common_device.h:377-386)
-	if (equals_case_insensitive(s, "SiLU") || equals_case_insensitive(s, "Sine")) {
-		throw std::runtime_error("Activation '" + s + "' is not supported by FullyFusedMLP (it needs stored pre-activations).");
 	}
 	throw std::runtime_error("Invalid activation name: " + s);  // common_host.cu:94
 }
@@ -388,7 +385,7 @@ EncodingDesc create_encoding_desc(uint32_t n_dims, const Json& enc, uint32_t ali
 
 Json NetworkDesc::hyperparams() const {
 	Json j = Json::object();
-	j["otype"] = mlp_fused_width(mlp.width) ? "FullyFusedMLP" : "CutlassMLP";  // fully_fused_mlp.h:141, cutlass_mlp.h:152
+	j["otype"] = mlp_layer_by_layer(mlp) ? "CutlassMLP" : "FullyFusedMLP";  // cutlass_mlp.h:152, fully_fused_mlp.h:141
 	j["activation"] = to_string((Activation)mlp.activation);
 	j["output_activation"] = to_string((Activation)mlp.output_activation);
 	j["n_neurons"] = mlp.width;
@@ -406,23 +403,37 @@ static NetworkDesc create_network_desc(uint32_t n_input_dims, uint32_t n_output_
 	const uint32_t n_neurons = net.value("n_neurons", 128u);
 	// network.cu:51-77, 129-137: FullyFusedMLP exists for four widths; "MLP" / "CutlassMLP" take those where they can and the
 	// layer-by-layer network (mlp_general.hip) for every other multiple of 16
-	const bool fused = mlp_fused_width(n_neurons);
+	const bool fused_width = mlp_fused_width(n_neurons);
 	const bool wants_fused = equals_case_insensitive(otype, "MegakernelMLP") || equals_case_insensitive(otype, "FullyFusedMLP");
-	if (!fused && wants_fused) {
+	if (!fused_width && wants_fused) {
 		throw std::runtime_error("FullyFusedMLP only supports 16, 32, 64, and 128 neurons, but got " + std::to_string(n_neurons) +
 		                         ". Use CutlassMLP instead.");
 	}
-	if (!fused && n_neurons % 16 != 0) {
+	if (!fused_width && n_neurons % 16 != 0) {
 		throw std::runtime_error("CutlassMLP: the number of neurons must be a multiple of 16, but got " + std::to_string(n_neurons) + ".");
 	}
-	if (!fused && (n_neurons < 16 || n_neurons > MLP_GENERAL_MAX_WIDTH)) {
+	if (!fused_width && (n_neurons < 16 || n_neurons > MLP_GENERAL_MAX_WIDTH)) {
 		throw std::runtime_error("CutlassMLP: between 16 and " + std::to_string(MLP_GENERAL_MAX_WIDTH) + " neurons are supported by this build, but got " + std::to_string(n_neurons) + ".");
 	}
+	// SiLU and Sine need stored pre-activations, which FullyFusedMLP does not keep (common_device.h:377-386): as hidden activations they
+	// make a network of ANY width a layer-by-layer one (cutlass_mlp.cu:53: no fused activation epilogue either); as output activations
+	// nobody's backward pass has them (common_device.h:375-390 is an empty case) -- refused instead of a silently missing derivative
+	const std::string act_name = net.value("activation", "ReLU"), out_act_name = net.value("output_activation", "None");
+	const Activation act = string_to_activation(act_name);
+	const Activation out_act = string_to_activation(out_act_name);
+	if (act_needs_preactivation((uint32_t)act) && wants_fused) {
+		throw std::runtime_error("Activation '" + act_name + "' is not supported by FullyFusedMLP (it needs stored pre-activations); use CutlassMLP.");
+	}
+	if (act_needs_preactivation((uint32_t)out_act)) {
+		throw std::runtime_error("Activation '" + out_act_name + "' is not supported as output_activation: output activations must be expressible from the output value "
+		                         "(the backward pass takes their derivative at the stored output; this one needs the pre-activation).");
+	}
+	d.mlp.width = n_neurons;
+	d.mlp.activation = (uint32_t)act;
+	const bool fused = !mlp_layer_by_layer(d.mlp);
 	const char* const name = fused ? "FullyFusedMLP" : "CutlassMLP";
 	d.n_hidden_layers = net.value("n_hidden_layers", 5u);
 	if (d.n_hidden_layers == 0) throw std::runtime_error(std::string(name) + " requires at least 1 hidden layer (3 layers in total).");
-	const Activation act = string_to_activation(net.value("activation", "ReLU"));
-	const Activation out_act = string_to_activation(net.value("output_activation", "None"));
 	d.n_output_dims = n_output_dims;
 	d.mlp.in_width = n_input_dims;
 	d.mlp.width = n_neurons;
@@ -456,8 +467,8 @@ void Model::initialize_params(hipStream_t stream, Pcg32& rng, float* params_full
 	if (has_network) {
 		std::vector<float> host(n_mlp_params());
 		float* p = host.data();
-		auto xavier = [&](uint32_t rows, uint32_t cols) {  // gpu_matrix.h:292-307
-			const float s = scale * std::sqrt(6.0f / (float)(rows + cols));
+		// uniform in [-s, s): next_float() * 2 * s - s, every step rounded to fp32 on its own (separate statements: no contraction)
+		auto uniform = [&](uint32_t rows, uint32_t cols, float s) {
 			for (size_t i = 0; i < (size_t)rows * cols; ++i) {
 				float t = rng.next_float() * 2.0f;
 				t = t * s;
@@ -465,9 +476,25 @@ void Model::initialize_params(hipStream_t stream, Pcg32& rng, float* params_full
 			}
 			p += (size_t)rows * cols;
 		};
-		xavier(net.mlp.width, net.mlp.in_width);
-		for (uint32_t i = 0; i < net.mlp.n_hidden_matmuls; ++i) xavier(net.mlp.width, net.mlp.width);
-		xavier(net.mlp.padded_out, net.mlp.width);
+		auto xavier = [&](uint32_t rows, uint32_t cols) { uniform(rows, cols, scale * std::sqrt(6.0f / (float)(rows + cols))); };  // gpu_matrix.h:292-307
+		// SIREN (gpu_matrix.h:343-377, cutlass_mlp.cu:362-371): the first matrix 30 / fan_in, every other one sqrt(6 / fan_in); same rng, same order
+		auto siren_first = [&](uint32_t rows, uint32_t cols) {
+			const float f = 30.0f / (float)cols;
+			uniform(rows, cols, scale * f);
+		};
+		auto siren = [&](uint32_t rows, uint32_t cols) {
+			const float f = std::sqrt(6.0f / (float)cols);
+			uniform(rows, cols, scale * f);
+		};
+		if (net.mlp.activation == (uint32_t)Activation::Sine) {
+			siren_first(net.mlp.width, net.mlp.in_width);
+			for (uint32_t i = 0; i < net.mlp.n_hidden_matmuls; ++i) siren(net.mlp.width, net.mlp.width);
+			siren(net.mlp.padded_out, net.mlp.width);
+		} else {
+			xavier(net.mlp.width, net.mlp.in_width);
+			for (uint32_t i = 0; i < net.mlp.n_hidden_matmuls; ++i) xavier(net.mlp.width, net.mlp.width);
+			xavier(net.mlp.padded_out, net.mlp.width);
+		}
 		HIP_CHECK(hipMemcpyAsync(params_full_precision, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, stream));
 		HIP_CHECK(hipStreamSynchronize(stream));
 	}

@@ -182,6 +182,7 @@ void encoding_forward(hipStream_t stream, Profiler* profiler, const Model& md, c
 	}
 }
 
+// (mlp_train_supported is false for every mlp_layer_by_layer() network: those always save their activations)
 static bool backward_recomputes(const Model& md) { return g_fused_network_passes.load() != 0 && md.has_network && mlp_train_supported(md.net.mlp); }
 
 // NetworkWithInputEncoding::forward_impl / inference_mixed_precision_impl (:60-81).  ctx == nullptr: inference.
@@ -222,7 +223,7 @@ void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, cons
 	encoding_forward(stream, profiler, md, layout, n, input, params + md.n_mlp_params(), enc.as<half_t>(), /*soa=*/true, dy_dx, ctx, prepare_input_gradients);
 	half_t* hidden = nullptr;
 	if (ctx && !backward_recomputes(md)) {
-		ctx->hidden = Scratch(stream, (size_t)md.net.n_hidden_layers * n * md.net.mlp.width * sizeof(half_t));
+		ctx->hidden = Scratch(stream, mlp_saved_activation_bytes(md.net.mlp, n));
 		hidden = ctx->hidden.as<half_t>();
 	}
 	ProfScope prof(profiler, stream, STAGE_MLP_FWD);
@@ -249,7 +250,8 @@ void inference_to_f32(hipStream_t stream, const Model& md, const IoLayout& layou
 
 uint32_t widest_matrix(const Model& md) {
 	uint32_t w = std::max(md.enc.padded_output_width, md.n_input_dims);
-	if (md.has_network) w = std::max(w, std::max(md.net.mlp.width * md.net.n_hidden_layers, md.net.mlp.padded_out));
+	// (the saved stack of one sample, in elements: twice the hidden layers where the pre-activations are kept)
+	if (md.has_network) w = std::max(w, std::max((uint32_t)(mlp_saved_activation_bytes(md.net.mlp, 1u) / sizeof(half_t)), md.net.mlp.padded_out));
 	if (md.enc.is_grid()) w = std::max(w, md.enc.n_output_dims * md.n_input_dims);  // dy_dx
 	w = std::max(w, md.enc.unreduced_width());  // a Composite's Sum / Product
 	for (const EncodingDesc& e : md.enc.nested) {
