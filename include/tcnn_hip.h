@@ -253,17 +253,29 @@ int tcnn_trainer_set_gradient_exchange(tcnn_trainable_model_t* tm, void (*exchan
  * synchronisation on either call in the steady state; tcnn_free_temporary_memory() releases the cache. */
 int tcnn_stream_malloc(tcnn_stream_t stream, size_t bytes, void** out, size_t* granted);
 int tcnn_stream_free(tcnn_stream_t stream, void* ptr, size_t granted);
-/* Optimizer<T> on its own (reference optimizer.h:40-99, optimizers/adam.h): Adam over weight buffers the host owns.
- * create (JSON as in the "optimizer" block; otype Adam) -> allocate(n_weights, n_matrix_weights: the leading parameters that are matrix
- * weights, adam.h:79-110) -> step(stream, loss_scale, fp32 weights, 16-bit weights, 16-bit gradients scaled by loss_scale), any number of
- * times.  Same kernel and arithmetic as the trainer's optimizer step. */
+/* Optimizer<T> on its own (reference optimizer.h:40-99, optimizers/): an optimizer over weight buffers the host owns.
+ * create (JSON as in the "optimizer" block: any order of the wrappers Ema, ExponentialDecay, Lookahead, Average, Batched, each at most once,
+ * around one base out of Adam, SGD, Novograd; Composite and Shampoo are refused) -> allocate -> step any number of times.  Same kernels
+ * and arithmetic as the trainer's optimizer step.
+ * allocate_layers: the n_layers weight matrices of rows[l] x cols[l] lead the parameter vector (Adam's weight decay / l2_reg apply to them,
+ * Novograd steps them alone, layer by layer); allocate(n_weights, n_matrix_weights) means one layer of n_matrix_weights weights. */
 typedef struct tcnn_optimizer tcnn_optimizer_t;
 int tcnn_create_optimizer(const char* optimizer_json, tcnn_optimizer_t** out);
 int tcnn_optimizer_allocate(tcnn_optimizer_t* o, size_t n_weights, size_t n_matrix_weights);
+int tcnn_optimizer_allocate_layers(tcnn_optimizer_t* o, size_t n_weights, size_t n_layers, const uint32_t* rows, const uint32_t* cols);
 int tcnn_optimizer_step(tcnn_optimizer_t* o, tcnn_stream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients);
-uint32_t tcnn_optimizer_step_count(const tcnn_optimizer_t* o);
+uint32_t tcnn_optimizer_step_count(const tcnn_optimizer_t* o); /* Optimizer::step(): Batched reports its own calls, the other wrappers the nested count */
 int tcnn_optimizer_update_hyperparams(tcnn_optimizer_t* o, const char* optimizer_json);
-void* tcnn_optimizer_state(tcnn_optimizer_t* o, int which); /* 0 first moments, 1 second moments (fp32), 2 step counters (u32) */
+const char* tcnn_optimizer_hyperparams_json(tcnn_optimizer_t* o); /* Optimizer::hyperparams(); valid until the next call on `o` */
+void* tcnn_optimizer_state(tcnn_optimizer_t* o, int which); /* Adam base only: 0 first moments, 1 second moments (fp32), 2 step counters (u32) */
+/* a state buffer by its snapshot key without "_binary" (first_moments, per_layer_second_moments, weights_ema, weights_lookahead,
+ * weights_average, weights_samples, averaged_gradients, averaged_gradients_half, ...): device pointer, element count, bytes per element */
+int tcnn_optimizer_state_named(tcnn_optimizer_t* o, const char* name, void** ptr, size_t* count, size_t* elem_bytes);
+/* Optimizer::serialize / deserialize: the state as the MessagePack bytes of the reference's JSON document (what the "optimizer" member of
+ * tcnn_trainer_serialize holds).  buffer == NULL: *n_bytes = the size needed. */
+int tcnn_optimizer_serialize(tcnn_optimizer_t* o, void* buffer, size_t capacity, size_t* n_bytes);
+int tcnn_optimizer_deserialize(tcnn_optimizer_t* o, const void* data, size_t n_bytes);
+void* tcnn_optimizer_custom_weights(tcnn_optimizer_t* o); /* Optimizer::custom_weights(): the outermost wrapper's inference weights, or NULL */
 void tcnn_optimizer_destroy(tcnn_optimizer_t* o);
 /* Loss<T>::evaluate on its own (reference loss.h:42-50 and the headers under losses/): `loss_otype` as in the JSON ("RelativeL2", "L2", "L1", ...).
  * prediction / gradients: column-major `stride` x n matrices of the library's 16-bit type (stride = padded output width, a multiple of
@@ -320,6 +332,9 @@ int tcnn_trainer_direct_selftest(tcnn_trainable_model_t* tm, tcnn_stream_t strea
 /* Adam's state (device pointers, n_params elements each): which = 0 first moments (fp32), 1 second moments (fp32),
  * 2 per-parameter step counters (u32; *steps_are_deficits = 1: the array holds `optimizer steps done - counter`). */
 void* tcnn_trainer_optimizer_state(tcnn_trainable_model_t* tm, int which, int* steps_are_deficits);
+/* The same for any optimizer (tcnn_optimizer_state_named); tcnn_trainer_optimizer_state returns NULL and sets the last error when the
+ * base optimizer is not Adam. */
+int tcnn_trainer_optimizer_state_named(tcnn_trainable_model_t* tm, const char* name, void** ptr, size_t* count, size_t* elem_bytes);
 
 /* Measurement hooks (no reference counterpart): HIP events recorded around each stage of the training step
  * on the stream the kernels are launched on.  only_stage < 0 times every stage, otherwise just that one.

@@ -1,84 +1,116 @@
 // api_optimizer.hip -- C ABI: the stand-alone optimizer (tcnn_optimizer_*) and tcnn_loss_evaluate, for hosts that drive the passes themselves.
+#include <cstring>
 #include <memory>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "device_alloc.h"
 #include "host_common.h"
 #include "model_desc.h"
+#include "optimizer_chain.h"
 
 using namespace tcnn_hip;
 
 extern "C" {
 
-// Optimizer<T> on its own (optimizer.h:40-99, optimizers/adam.h:130-219): Adam over weight buffers the HOST owns -- for callers that
-// drive forward / loss / backward themselves.  The same kernel and arithmetic as the trainer's optimizer step (counter form of the
+// Optimizer<T> on its own (optimizer.h:40-99): an optimizer chain (optimizer_chain.h) over weight buffers the HOST owns -- for callers that
+// drive forward / loss / backward themselves.  The same kernels and arithmetic as the trainer's optimizer step (Adam: counter form of the
 // per-parameter step counters).
 struct tcnn_optimizer {
-	AdamHyper adam;
-	uint32_t n = 0, n_matrix = 0, step = 0;
-	float *m1 = nullptr, *m2 = nullptr;
-	uint32_t* steps = nullptr;
+	std::unique_ptr<OptimizerChain> chain;
+	std::string hyper_json;
 };
 int tcnn_create_optimizer(const char* optimizer_json, tcnn_optimizer_t** out) {
 	TCNN_API_BEGIN
-	const Json opts = Json::parse(optimizer_json ? optimizer_json : "{}");
-	const std::string otype = opts.value("otype", "Adam");
-	if (!equals_case_insensitive(otype, "Adam")) throw std::runtime_error("Optimizer '" + otype + "' is not available as a stand-alone object in this build (supported: Adam).");
 	auto o = std::make_unique<tcnn_optimizer>();
-	parse_adam(o->adam, opts);
+	o->chain = std::make_unique<OptimizerChain>(Json::parse(optimizer_json ? optimizer_json : "{}"));
 	*out = o.release();
 	TCNN_API_END
 }
-static void optimizer_release(tcnn_optimizer_t* o) {
-	device_free(o->m1);
-	device_free(o->m2);
-	device_free(o->steps);
-	o->m1 = o->m2 = nullptr;
-	o->steps = nullptr;
-}
-// Optimizer::allocate(n_weights, layer_sizes): the first n_matrix_weights parameters are matrix weights (weight decay / l2_reg apply to
-// them, adam.h:79-110), the rest (e.g. an encoding's) are not
-int tcnn_optimizer_allocate(tcnn_optimizer_t* o, size_t n_weights, size_t n_matrix_weights) {
+// Optimizer::allocate(n_weights, layer_sizes): the layers' weight matrices lead the parameter vector (weight decay / l2_reg of Adam apply to
+// them, adam.h:79-110; Novograd steps them alone, layer by layer), the rest (e.g. an encoding's) are no matrix weights
+int tcnn_optimizer_allocate_layers(tcnn_optimizer_t* o, size_t n_weights, size_t n_layers, const uint32_t* rows, const uint32_t* cols) {
 	TCNN_API_BEGIN
-	if (n_weights > 0xFFFFFFFFull || n_matrix_weights > n_weights) throw std::runtime_error("Optimizer::allocate: bad sizes");
-	(void)hipDeviceSynchronize();
-	optimizer_release(o);
-	o->n = (uint32_t)n_weights;
-	o->n_matrix = (uint32_t)n_matrix_weights;
-	o->step = 0;
-	if (o->n) {
-		o->m1 = device_malloc_n<float>(o->n);
-		o->m2 = device_malloc_n<float>(o->n);
-		o->steps = device_malloc_n<uint32_t>(o->n);
-		HIP_CHECK(hipMemset(o->m1, 0, (size_t)o->n * sizeof(float)));
-		HIP_CHECK(hipMemset(o->m2, 0, (size_t)o->n * sizeof(float)));
-		HIP_CHECK(hipMemset(o->steps, 0, (size_t)o->n * sizeof(uint32_t)));
-	}
+	if (n_weights > 0xFFFFFFFFull || (n_layers && (!rows || !cols))) throw std::runtime_error("Optimizer::allocate: bad sizes");
+	std::vector<std::pair<uint32_t, uint32_t>> layers;
+	for (size_t l = 0; l < n_layers; ++l) layers.emplace_back(rows[l], cols[l]);
+	o->chain->allocate((uint32_t)n_weights, layers);
 	TCNN_API_END
+}
+// one layer of n_matrix_weights x 1 when n_matrix_weights > 0
+int tcnn_optimizer_allocate(tcnn_optimizer_t* o, size_t n_weights, size_t n_matrix_weights) {
+	if (n_matrix_weights > 0xFFFFFFFFull) n_matrix_weights = 0xFFFFFFFFull;  // (refused below: more than n_weights can hold)
+	const uint32_t rows = (uint32_t)n_matrix_weights, cols = 1u;
+	return tcnn_optimizer_allocate_layers(o, n_weights, n_matrix_weights > 0 ? 1 : 0, &rows, &cols);
 }
 // Optimizer::step (optimizer.h:58): gradients carry the loss scale; weights_full_precision and weights (16-bit) are both updated
 int tcnn_optimizer_step(tcnn_optimizer_t* o, tcnn_stream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) {
 	TCNN_API_BEGIN
-	if (!o->n) return TCNN_OK;
+	if (!o->chain->n_weights()) return TCNN_OK;
 	if (!weights_full_precision || !weights || !gradients) throw std::runtime_error("Optimizer::step: missing buffer");
-	++o->step;  // adam.h:159
-	adam_step((hipStream_t)stream, o->adam, o->n, o->n_matrix, loss_scale, o->step, weights_full_precision, (half_t*)weights, (half_t*)gradients /* read only: no finalize rides along */, o->m1, o->m2, o->steps);
+	o->chain->step((hipStream_t)stream, loss_scale, weights_full_precision, (half_t*)weights, (const half_t*)gradients);
 	TCNN_API_END
 }
-uint32_t tcnn_optimizer_step_count(const tcnn_optimizer_t* o) { return o->step; }
+uint32_t tcnn_optimizer_step_count(const tcnn_optimizer_t* o) { return o->chain->step_count(); }
 int tcnn_optimizer_update_hyperparams(tcnn_optimizer_t* o, const char* optimizer_json) {
 	TCNN_API_BEGIN
-	parse_adam(o->adam, Json::parse(optimizer_json ? optimizer_json : "{}"));
+	o->chain->update_hyperparams(Json::parse(optimizer_json ? optimizer_json : "{}"));
 	TCNN_API_END
 }
-// which = 0 first moments, 1 second moments (fp32), 2 per-parameter step counters (u32); device pointers, n_weights elements each
-void* tcnn_optimizer_state(tcnn_optimizer_t* o, int which) { return which == 0 ? (void*)o->m1 : which == 1 ? (void*)o->m2 : which == 2 ? (void*)o->steps : nullptr; }
-void tcnn_optimizer_destroy(tcnn_optimizer_t* o) {
-	if (!o) return;
-	(void)hipDeviceSynchronize();
-	optimizer_release(o);
-	delete o;
+const char* tcnn_optimizer_hyperparams_json(tcnn_optimizer_t* o) {
+	o->hyper_json = o->chain->hyperparams().dump();
+	return o->hyper_json.c_str();
 }
+// Adam's buffers: which = 0 first moments, 1 second moments (fp32), 2 per-parameter step counters (u32); device pointers, n_weights elements each
+void* tcnn_optimizer_state(tcnn_optimizer_t* o, int which) {
+	void* p = nullptr;
+	if (o->chain->base() != OptimizerChain::Kind::Adam) {
+		set_last_error("tcnn_optimizer_state: the base optimizer is not Adam (use tcnn_optimizer_state_named)");
+		return nullptr;
+	}
+	o->chain->state_named(which == 0 ? "first_moments" : which == 1 ? "second_moments" : which == 2 ? "param_steps" : "", &p, nullptr, nullptr);
+	return p;
+}
+// any state buffer of the chain by its snapshot key without "_binary" (weights_lookahead, weights_average, weights_samples, averaged_gradients,
+// averaged_gradients_half, first_moments, per_layer_second_moments, weights_ema, ...): device pointer, element count, bytes per element
+int tcnn_optimizer_state_named(tcnn_optimizer_t* o, const char* name, void** ptr, size_t* count, size_t* elem_bytes) {
+	TCNN_API_BEGIN
+	if (!name || !o->chain->state_named(name, ptr, count, elem_bytes)) throw std::runtime_error(std::string("Optimizer: no state buffer named '") + (name ? name : "") + "' in this optimizer");
+	TCNN_API_END
+}
+// Optimizer::custom_weights(): the outermost wrapper's inference weights (Ema's average, Lookahead's slow weights, Average's mean), or null
+void* tcnn_optimizer_custom_weights(tcnn_optimizer_t* o) { return o->chain->custom_weights(); }
+// Optimizer::serialize() / deserialize(): the state as the MessagePack bytes of the reference's JSON document (snapshot_msgpack.h; the
+// "optimizer" member of a trainer snapshot).  buffer == NULL: *n_bytes = the size needed.
+int tcnn_optimizer_serialize(tcnn_optimizer_t* o, void* buffer, size_t capacity, size_t* n_bytes) {
+	TCNN_API_BEGIN
+	std::vector<uint8_t> header;
+	msgpack_detail::Writer count{header, true};
+	o->chain->write_state(count);
+	const size_t needed = header.size() + count.skipped;
+	if (n_bytes) *n_bytes = needed;
+	if (buffer) {
+		if (capacity < needed) throw std::runtime_error("tcnn_optimizer_serialize: buffer too small");
+		HIP_CHECK(hipDeviceSynchronize());
+		std::vector<uint8_t> bytes;
+		bytes.reserve(needed);
+		msgpack_detail::Writer w{bytes};
+		o->chain->write_state(w);
+		std::memcpy(buffer, bytes.data(), bytes.size());
+	}
+	TCNN_API_END
+}
+int tcnn_optimizer_deserialize(tcnn_optimizer_t* o, const void* data, size_t n_bytes) {
+	TCNN_API_BEGIN
+	if (!data) throw std::runtime_error("tcnn_optimizer_deserialize: null data");
+	HIP_CHECK(hipDeviceSynchronize());
+	msgpack_detail::Reader r{(const uint8_t*)data, (const uint8_t*)data + n_bytes};
+	o->chain->read_state(r);
+	HIP_CHECK(hipDeviceSynchronize());
+	TCNN_API_END
+}
+void tcnn_optimizer_destroy(tcnn_optimizer_t* o) { delete o; }
 
 // Loss<T>::evaluate (loss.h:42-50) on its own: prediction / gradients are column-major `stride` x n matrices in the library's 16-bit
 // type (= sample-major [n][stride]), target / data_pdf `dims` x n fp32, values `stride` x n fp32 (may be null); rows >= dims carry no

@@ -4,6 +4,7 @@
 #include <memory>
 #include <random>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "device_alloc.h"
@@ -62,13 +63,25 @@ int tcnn_create_from_config(uint32_t n_input_dims, uint32_t n_output_dims, const
 	tm->master = (float*)tm->buffer;
 	tm->params = (half_t*)((char*)tm->buffer + sizeof(float) * n);
 	tm->grads = tm->params + n;
-	tm->m1 = device_malloc_n<float>(n);  // adam.h:136-156
-	tm->m2 = device_malloc_n<float>(n);
-	tm->steps = device_malloc_n<uint32_t>(n);
-	tm->step_deficits8 = device_malloc_n<uint8_t>(n);
-	HIP_CHECK(hipMemset(tm->m1, 0, n * sizeof(float)));
-	HIP_CHECK(hipMemset(tm->m2, 0, n * sizeof(float)));
-	HIP_CHECK(hipMemset(tm->steps, 0, n * sizeof(uint32_t)));
+	if (tm->chain) {  // Optimizer::allocate(n_params, layer_sizes), trainer.h:66: the network's weight matrices (object.h layer_sizes())
+		std::vector<std::pair<uint32_t, uint32_t>> layers;
+		if (tm->md.has_network) {
+			const MlpMeta& m = tm->md.net.mlp;
+			layers.emplace_back(m.width, m.in_width);
+			for (uint32_t l = 0; l < m.n_hidden_matmuls; ++l) layers.emplace_back(m.width, m.width);
+			layers.emplace_back(m.padded_out, m.width);
+		}
+		if (n > 0xFFFFFFFFull) throw std::runtime_error("Optimizer::allocate: bad sizes");
+		tm->chain->allocate((uint32_t)n, layers);
+	} else {
+		tm->m1 = device_malloc_n<float>(n);  // adam.h:136-156
+		tm->m2 = device_malloc_n<float>(n);
+		tm->steps = device_malloc_n<uint32_t>(n);
+		tm->step_deficits8 = device_malloc_n<uint8_t>(n);
+		HIP_CHECK(hipMemset(tm->m1, 0, n * sizeof(float)));
+		HIP_CHECK(hipMemset(tm->m2, 0, n * sizeof(float)));
+		HIP_CHECK(hipMemset(tm->steps, 0, n * sizeof(uint32_t)));
+	}
 	if (tm->ema) {  // ema.h:90-102
 		tm->params_ema = device_malloc_n<half_t>(n);
 		HIP_CHECK(hipMemset(tm->params_ema, 0, n * sizeof(half_t)));
@@ -266,7 +279,7 @@ static int training_step_fused(tcnn_trainable_model_t* tm, hipStream_t stream, c
 		                                  input_by_network ? &f32_input : nullptr);
 		// The slabs' sums: by the first workgroups of the optimizer's launch when this call runs the whole step itself on one GPU (nobody reads
 		// the network's gradients between here and there: no exchange, no ready callback, no accumulation) -- by their own kernel otherwise.
-		const bool sum_in_optimizer = want_grads && run_optimizer && !accumulate && !tm->exchange && !tm->direct.active() && !wants_ready_ranges(tm) &&
+		const bool sum_in_optimizer = want_grads && run_optimizer && !accumulate && !tm->chain && !tm->exchange && !tm->direct.active() && !wants_ready_ranges(tm) &&
 		                              md.n_mlp_params() % 4 == 0 && g_finalize_in_optimizer.load() != 0;
 		if (sum_in_optimizer) {
 			tm->pending_finalize.partials = partials.as<float>();
@@ -310,6 +323,9 @@ static int training_step_fused_captured(tcnn_trainable_model_t* tm, tcnn_stream_
 		(void)hipGetLastError();
 		capture = false;
 	}
+	// an optimizer chain's launches change from step to step (Lookahead's pull, Batched's nested step): the instantiated graph is only
+	// patched by a step of the same launches, any other one instantiates anew
+	const uint32_t signature = tm->chain && run_optimizer ? tm->chain->next_step_signature() : 0u;
 	int r = training_step_fused(tm, (hipStream_t)stream, layout, loss_scale, n, input, target, data_pdf, dL_dinput, use_inference_params, gradient_mode,
 	                            run_optimizer != 0, (const half_t*)external_dL_dy, ctx, context_wanted);
 	if (capture) {
@@ -322,6 +338,11 @@ static int training_step_fused_captured(tcnn_trainable_model_t* tm, tcnn_stream_
 			r = TCNN_ERROR;
 		}
 		if (r == TCNN_OK) {
+			if (tm->graph_exec && signature != tm->graph_signature) {
+				(void)hipGraphExecDestroy(tm->graph_exec);
+				tm->graph_exec = nullptr;
+			}
+			tm->graph_signature = signature;
 			if (tm->graph_exec) {  // patch the instantiated graph with this step's arguments (cuda_graph.h:118-138); a new topology re-instantiates
 				hipGraphNode_t error_node = nullptr;
 				hipGraphExecUpdateResult result = hipGraphExecUpdateSuccess;
@@ -549,7 +570,7 @@ void* tcnn_trainer_params(tcnn_trainable_model_t* tm) {
 	return tm->params;
 }
 void* tcnn_trainer_params_inference(tcnn_trainable_model_t* tm) {
-	if (!tm->ema) tm->params_exposed = true;  // the same buffer as `params` (trainer.h:497-500)
+	if (!tm->has_custom_weights()) tm->params_exposed = true;  // the same buffer as `params` (trainer.h:497-500)
 	return tm->inference_params();
 }
 void* tcnn_trainer_param_gradients(tcnn_trainable_model_t* tm) { return tm->grads; }

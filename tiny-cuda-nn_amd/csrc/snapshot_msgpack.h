@@ -14,6 +14,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -26,6 +27,11 @@ struct SnapshotBlob {
 	std::vector<uint8_t> owned;  // backing store when the input was a {"bytes":[...]} array
 	bool present() const { return data != nullptr; }
 };
+
+namespace msgpack_detail {
+struct Writer;
+struct Reader;
+}
 
 struct Snapshot {
 	uint64_t n_params = 0;
@@ -41,6 +47,8 @@ struct Snapshot {
 	SnapshotBlob weights_ema;
 	bool has_decay = false;
 	float decay_learning_rate = 0.f, decay_learning_rate_factor = 1.f;
+	// any other optimizer (optimizer_chain.h) writes its state map itself, in place of the fields above
+	std::function<void(msgpack_detail::Writer&)> optimizer_writer;
 };
 
 namespace msgpack_detail {
@@ -274,7 +282,8 @@ inline void msgpack_detail::write_snapshot(Writer& w, const Snapshot& s) {
 	w.str("n_params"); w.uint(s.n_params);
 	if (s.has_optimizer) {
 		w.str("optimizer");
-		write_optimizer(w, s, 0);
+		if (s.optimizer_writer) s.optimizer_writer(w);
+		else write_optimizer(w, s, 0);
 	}
 	w.str("params_binary"); w.bin(s.params.data, s.params.size);
 	w.str("params_type"); w.str(s.params_type);
@@ -298,8 +307,9 @@ inline void msgpack_detail::read_optimizer(Reader& r, Snapshot& s) {
 	}
 }
 
-// Blobs point into [data, data + size) unless they came from a {"bytes":[...]} array.
-inline Snapshot snapshot_decode(const uint8_t* data, size_t size) {
+// Blobs point into [data, data + size) unless they came from a {"bytes":[...]} array.  optimizer_reader (optional): reads the "optimizer"
+// map itself (optimizer_chain.h) instead of the Adam / Ema / ExponentialDecay fields.
+inline Snapshot snapshot_decode(const uint8_t* data, size_t size, const std::function<void(msgpack_detail::Reader&)>& optimizer_reader = {}) {
 	msgpack_detail::Reader r{data, data + size};
 	Snapshot s;
 	bool have_type = false;
@@ -310,7 +320,8 @@ inline Snapshot snapshot_decode(const uint8_t* data, size_t size) {
 		else if (key == "params_binary") r.blob(s.params);
 		else if (key == "optimizer") {
 			s.has_optimizer = true;
-			msgpack_detail::read_optimizer(r, s);
+			if (optimizer_reader) optimizer_reader(r);
+			else msgpack_detail::read_optimizer(r, s);
 		} else r.skip();
 	}
 	(void)have_type;  // absent -> the trainer's own parameter type, trainer.h:458

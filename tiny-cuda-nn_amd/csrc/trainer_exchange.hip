@@ -172,7 +172,7 @@ void finish_training_step(tcnn_trainable_model_t* tm, hipStream_t stream, float 
 		HIP_CHECK(hipStreamWaitEvent(tm->comm_stream, stepped, 0));
 		const int type = HALF_IS_BF16 ? RCCL_BFLOAT16 : RCCL_HALF;
 		if (r.group_start) rccl_check(r, r.group_start(), "ncclGroupStart");
-		for (half_t* buf : {tm->params, tm->ema ? tm->params_ema : (half_t*)nullptr}) {
+		for (half_t* buf : {tm->params, tm->has_custom_weights() ? tm->inference_params() : (half_t*)nullptr}) {
 			if (!buf) continue;
 			for (const auto& rr : ranges) {
 				if (rr.shard) rccl_check(r, r.all_gather(buf + rr.begin + me * rr.shard, buf + rr.begin, rr.shard, type, tm->rccl_comm, tm->comm_stream), "ncclAllGather");
@@ -221,6 +221,7 @@ int tcnn_trainer_set_backward_level_groups(tcnn_trainable_model_t* tm, uint32_t 
 // finished.  The host sets the global batch size (tcnn_trainer_set_global_batch_size) so that the sum is the global gradient.
 static void enable_rccl(tcnn_trainable_model_t* tm, void* nccl_comm, int n_ranks, int rank) {
 	if (nccl_comm) {
+		require_ranged_optimizer(tm, rank >= 0 ? "tcnn_trainer_enable_rccl_sharded" : "tcnn_trainer_enable_rccl");  // every reduced range is stepped on its own
 		const Rccl& r = Rccl::get();
 		if (!r.handle || !r.all_reduce) throw std::runtime_error("tcnn_trainer_enable_rccl: librccl.so could not be loaded");
 		if (rank >= 0 && (!r.reduce_scatter || !r.all_gather)) throw std::runtime_error("tcnn_trainer_enable_rccl_sharded: librccl.so lacks ncclReduceScatter / ncclAllGather");
@@ -258,7 +259,8 @@ int tcnn_trainer_direct_export(tcnn_trainable_model_t* tm, void* out, size_t cap
 	if (!out) return TCNN_OK;
 	if (capacity < sizeof(DirectExport)) throw std::runtime_error("tcnn_trainer_direct_export: buffer too small");
 	if (debug_alloc_mode() != DebugAlloc::Off) throw std::runtime_error("tcnn_trainer_direct_export: not available under TCNN_DEBUG_ALLOC (the trainer buffer must be a plain hipMalloc block)");
-	if (tm->ema) throw std::runtime_error("tcnn_trainer_direct_export: Ema-wrapped optimizers are not supported by the direct exchange (use the sharded collective scheme)");
+	require_ranged_optimizer(tm, "tcnn_trainer_direct_export");  // the direct exchange steps this rank's shard of the parameters
+	if (tm->has_custom_weights()) throw std::runtime_error("tcnn_trainer_direct_export: Ema-wrapped optimizers are not supported by the direct exchange (use the sharded collective scheme)");
 	HIP_CHECK(hipDeviceSynchronize());
 	direct_exchange_export(tm->direct, tm->buffer, tm->params, tm->grads, tm->md.n_params(), *(DirectExport*)out);
 	TCNN_API_END

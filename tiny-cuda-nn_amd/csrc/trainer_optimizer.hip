@@ -1,5 +1,6 @@
-// trainer_optimizer.hip -- the trainer's optimizer: Adam inside optional Ema / ExponentialDecay wrappers -- its JSON, the (ranged)
-// optimizer step, the representation of the per-parameter step counters.
+// trainer_optimizer.hip -- the trainer's optimizer: Adam inside optional Ema / ExponentialDecay wrappers on the trainer's own fields (with
+// the fast paths that belong to Adam), any other chain through OptimizerChain -- its JSON, the (ranged) optimizer step, the representation
+// of the per-parameter step counters.
 #include <algorithm>
 #include <string>
 
@@ -10,7 +11,30 @@ namespace tcnn_hip {
 
 // optimizer.cu:50-86 for the optimizers of this build: Adam, optionally inside Ema / ExponentialDecay wrappers.
 // `creating`: build the chain from the config; otherwise walk the existing chain (update_hyperparams, trainer.h:380-383).
+// does the configuration name an optimizer that only OptimizerChain implements (or refuses by a name of its own)?
+static bool names_chain_optimizer(const Json& opts) {
+	Json cur = opts;
+	for (size_t depth = 0; depth < 16 && cur.is_object(); ++depth) {
+		const std::string otype = cur.value("otype", "Adam");
+		for (const char* name : {"SGD", "Novograd", "Lookahead", "Average", "Batched", "Composite"}) {
+			if (equals_case_insensitive(otype, name)) return true;
+		}
+		if (!cur.contains("nested")) break;
+		cur = cur.value("nested", Json::object());
+	}
+	return false;
+}
+
 void apply_optimizer_json(tcnn_trainable_model* tm, const Json& opts, bool creating) {
+	if (creating && names_chain_optimizer(opts)) {
+		tm->chain = std::make_unique<OptimizerChain>(opts);
+		return;
+	}
+	if (tm->chain) {
+		tm->chain->update_hyperparams(opts);
+		return;
+	}
+	if (!creating && names_chain_optimizer(opts)) throw std::runtime_error("update_hyperparams: optimizer structure does not match the trainer's");
 	Json cur = opts;
 	size_t depth = 0;
 	for (;;) {
@@ -51,7 +75,7 @@ void apply_optimizer_json(tcnn_trainable_model* tm, const Json& opts, bool creat
 			}
 			return;
 		} else {
-			throw std::runtime_error("Optimizer '" + otype + "' is not available in this build (supported: Adam, Ema, ExponentialDecay).");
+			throw std::runtime_error("Optimizer '" + otype + "' is not available in this build (supported: Adam, SGD, Novograd, Ema, ExponentialDecay, Lookahead, Average, Batched).");
 		}
 		if (!creating && !cur.contains("nested")) return;
 		cur = cur.value("nested", Json::object());
@@ -78,6 +102,7 @@ void refresh_hyper_json(tcnn_trainable_model* tm) {  // trainer.h:385-391, adam.
 	o["optimize_non_matrix_params"] = tm->adam.optimize_non_matrix_params;
 	o["skip_zero_grad_non_matrix_params"] = tm->adam.skip_zero_grad_non_matrix_params;
 	if (tm->lr_decay) o["learning_rate"] = tm->base_lr * tm->lr_factor;
+	if (tm->chain) o = tm->chain->hyperparams();
 	for (size_t k = tm->optimizer_order.size(); k-- > 0;) {  // wrap inside-out (ema.h:181-188, exponential_decay.h:116-125)
 		Json wrapper = Json::object();
 		if (tm->optimizer_order[k] == "Ema") {
@@ -173,6 +198,19 @@ void optimizer_step_ranges(tcnn_trainable_model_t* tm, hipStream_t stream, float
 	for (size_t r = 0; r < n_ranges; ++r) {
 		if (begins[r] % 8 != 0 || begins[r] > std::min(ends[r], n)) throw std::runtime_error("optimizer_step_range: a range must start at a multiple of 8 and not end before it");
 	}
+	if (tm->chain) {  // finished 16-bit gradients in, `params` out: the transposed copy is stale afterwards
+		const bool whole = n_ranges == 1 && begins[0] == 0 && ends[0] >= n && advance;
+		ProfScope prof(tm->profiler.get(), stream, STAGE_ADAM, opens_profiled_step, profile_any_stage);
+		if (whole) {
+			tm->chain->step(stream, loss_scale, tm->master, tm->params, tm->grads);
+		} else {
+			for (size_t r = 0; r < n_ranges; ++r) {
+				tm->chain->step_range(stream, loss_scale, tm->master, tm->params, tm->grads, (uint32_t)begins[r], (uint32_t)std::min(ends[r], n), advance && r == 0);
+			}
+		}
+		tm->params_t_valid = false;
+		return;
+	}
 	if (advance) optimizer_advance(tm, stream);
 	for (size_t r = 0; r < n_ranges; ++r) {
 		const size_t begin = begins[r], end = std::min(ends[r], n);
@@ -188,6 +226,7 @@ extern "C" {
 // One optimizer step == calls whose ranges tile [0, n_params) exactly once, the range with begin == 0 first.
 int tcnn_trainer_optimizer_step_range(tcnn_trainable_model_t* tm, tcnn_stream_t stream, float loss_scale, size_t begin, size_t end) {
 	TCNN_API_BEGIN
+	require_ranged_optimizer(tm, "optimizer_step_range");
 	optimizer_step_ranges(tm, (hipStream_t)stream, loss_scale, 1, &begin, &end, /*advance=*/begin == 0, begin == 0);
 	TCNN_API_END
 }
@@ -197,6 +236,7 @@ int tcnn_trainer_optimizer_step_range(tcnn_trainable_model_t* tm, tcnn_stream_t 
 int tcnn_trainer_optimizer_step_ranges(tcnn_trainable_model_t* tm, tcnn_stream_t stream, float loss_scale, size_t n_ranges, const size_t* begins,
                                        const size_t* ends) {
 	TCNN_API_BEGIN
+	require_ranged_optimizer(tm, "optimizer_step_ranges");
 	optimizer_step_ranges(tm, (hipStream_t)stream, loss_scale, n_ranges, begins, ends, /*advance=*/true, true);
 	TCNN_API_END
 }
@@ -204,6 +244,11 @@ int tcnn_trainer_optimizer_step_ranges(tcnn_trainable_model_t* tm, tcnn_stream_t
 }  // extern "C"
 
 namespace tcnn_hip {
+
+void require_ranged_optimizer(const tcnn_trainable_model* tm, const char* scheme) {
+	const char* who = tm->chain ? tm->chain->ranged_refusal() : nullptr;
+	if (who) throw std::runtime_error(std::string(scheme) + ": the " + who + " optimizer cannot step a range of the parameters (it needs the whole gradient in one call)");
+}
 
 void optimizer_step_all(tcnn_trainable_model_t* tm, hipStream_t stream, float loss_scale) {
 	const size_t begin = 0, end = tm->md.n_params();
@@ -215,12 +260,24 @@ void optimizer_step_all(tcnn_trainable_model_t* tm, hipStream_t stream, float lo
 extern "C" {
 
 int tcnn_trainer_optimizer_step(tcnn_trainable_model_t* tm, tcnn_stream_t stream, float loss_scale) {
-	return tcnn_trainer_optimizer_step_range(tm, stream, loss_scale, 0, tm->md.n_params());
+	TCNN_API_BEGIN
+	optimizer_step_all(tm, (hipStream_t)stream, loss_scale);  // (the whole vector in one call: every optimizer can)
+	TCNN_API_END
 }
 
 // Adam's state for snapshots / sharded data parallelism: which = 0 first moments (fp32), 1 second moments (fp32),
 // 2 per-parameter step counters (u32; *steps_are_deficits tells their representation, see tcnn_trainer_optimizer_step_range).
 void* tcnn_trainer_optimizer_state(tcnn_trainable_model_t* tm, int which, int* steps_are_deficits) {
+	if (tm->chain) {
+		void* p = nullptr;
+		if (steps_are_deficits) *steps_are_deficits = 0;
+		if (tm->chain->base() != OptimizerChain::Kind::Adam) {
+			set_last_error("tcnn_trainer_optimizer_state: the base optimizer is not Adam (use tcnn_trainer_optimizer_state_named)");
+			return nullptr;
+		}
+		tm->chain->state_named(which == 0 ? "first_moments" : which == 1 ? "second_moments" : which == 2 ? "param_steps" : "", &p, nullptr, nullptr);
+		return p;
+	}
 	if (which == 2 && tm->steps_form == ADAM_STEPS_DEFICITS8) {  // the byte form is the library's own business: hosts see counters
 		(void)hipDeviceSynchronize();
 		try {
@@ -235,6 +292,35 @@ void* tcnn_trainer_optimizer_state(tcnn_trainable_model_t* tm, int which, int* s
 	return which == 0 ? (void*)tm->m1 : which == 1 ? (void*)tm->m2 : which == 2 ? (void*)tm->steps : nullptr;
 }
 
+int tcnn_trainer_optimizer_state_named(tcnn_trainable_model_t* tm, const char* name, void** ptr, size_t* count, size_t* elem_bytes) {
+	TCNN_API_BEGIN
+	const std::string key = name ? name : "";
+	const size_t n = tm->md.n_params();
+	auto give = [&](void* p, size_t c, size_t e) {
+		if (ptr) *ptr = p;
+		if (count) *count = c;
+		if (elem_bytes) *elem_bytes = e;
+	};
+	if (tm->chain) {
+		if (!tm->chain->state_named(key, ptr, count, elem_bytes)) throw std::runtime_error("Optimizer: no state buffer named '" + key + "' in this optimizer");
+	} else if (key == "first_moments") {
+		give(tm->m1, n, 4);
+	} else if (key == "second_moments") {
+		give(tm->m2, n, 4);
+	} else if (key == "param_steps") {
+		int deficits = 0;
+		void* steps = tcnn_trainer_optimizer_state(tm, 2, &deficits);
+		if (!steps) return TCNN_ERROR;
+		if (deficits) throw std::runtime_error("Optimizer: the step counters are held as deficits (tcnn_trainer_optimizer_state tells the form)");
+		give(steps, n, 4);
+	} else if (key == "weights_ema" && tm->ema) {
+		give(tm->params_ema, n, 2);
+	} else {
+		throw std::runtime_error("Optimizer: no state buffer named '" + key + "' in this optimizer");
+	}
+	TCNN_API_END
+}
+
 int tcnn_trainer_update_hyperparams(tcnn_trainable_model_t* tm, const char* json) {
 	TCNN_API_BEGIN
 	const Json j = Json::parse(json);
@@ -246,6 +332,6 @@ const char* tcnn_trainer_hyperparams_json(tcnn_trainable_model_t* tm) {
 	refresh_hyper_json(tm);  // the learning rate moves with the ExponentialDecay schedule
 	return tm->hyper_json.c_str();
 }
-uint32_t tcnn_trainer_optimizer_step_count(const tcnn_trainable_model_t* tm) { return tm->optimizer_step; }
+uint32_t tcnn_trainer_optimizer_step_count(const tcnn_trainable_model_t* tm) { return tm->chain ? tm->chain->step_count() : tm->optimizer_step; }
 
 }  // extern "C"

@@ -21,6 +21,11 @@ static Snapshot snapshot_shape(const tcnn_trainable_model* tm, bool with_optimiz
 	s.params_type = NATIVE_TYPE_NAME;
 	s.params.size = n * sizeof(half_t);
 	s.has_optimizer = with_optimizer;
+	if (tm->chain) {
+		const OptimizerChain* chain = tm->chain.get();
+		s.optimizer_writer = [chain](msgpack_detail::Writer& w) { chain->write_state(w); };
+		return s;
+	}
 	s.current_step = tm->optimizer_step;
 	s.base_learning_rate = tm->adam.learning_rate;
 	s.first_moments.size = s.second_moments.size = n * sizeof(float);
@@ -46,7 +51,7 @@ int tcnn_trainer_serialize(tcnn_trainable_model_t* tm, int serialize_optimizer, 
 		std::vector<uint8_t> host_params(s.params.size), host_m1, host_m2, host_steps, host_ema;
 		HIP_CHECK(hipMemcpy(host_params.data(), tm->inference_params(), s.params.size, hipMemcpyDeviceToHost));  // trainer.h:448: params_inference
 		s.params.data = host_params.data();
-		if (s.has_optimizer) {
+		if (s.has_optimizer && !tm->chain) {
 			host_m1.resize(s.first_moments.size);
 			host_m2.resize(s.second_moments.size);
 			host_steps.resize(s.param_steps.size);
@@ -78,7 +83,12 @@ int tcnn_trainer_serialize(tcnn_trainable_model_t* tm, int serialize_optimizer, 
 
 int tcnn_trainer_deserialize(tcnn_trainable_model_t* tm, const void* data, size_t n_bytes) {
 	TCNN_API_BEGIN
-	const Snapshot s = snapshot_decode(static_cast<const uint8_t*>(data), n_bytes);
+	std::function<void(msgpack_detail::Reader&)> chain_reader;
+	if (tm->chain) {
+		HIP_CHECK(hipDeviceSynchronize());
+		chain_reader = [tm](msgpack_detail::Reader& r) { tm->chain->read_state(r); };
+	}
+	const Snapshot s = snapshot_decode(static_cast<const uint8_t*>(data), n_bytes, chain_reader);
 	const size_t n = tm->md.n_params();
 	if (s.params_type == "float") {
 		if (s.params.size != n * sizeof(float)) throw std::runtime_error("Can't set fp params because buffer has the wrong size.");  // trainer.h:410-412
@@ -93,7 +103,9 @@ int tcnn_trainer_deserialize(tcnn_trainable_model_t* tm, const void* data, size_
 	} else {
 		throw std::runtime_error(std::string("Trainer: snapshot parameters must be of type float of ") + NATIVE_TYPE_NAME);  // trainer.h:473
 	}
-	if (s.has_optimizer) {
+	if (s.has_optimizer && tm->chain) {
+		refresh_hyper_json(tm);
+	} else if (s.has_optimizer) {
 		if (!s.first_moments.present() || !s.second_moments.present() || s.first_moments.size != n * sizeof(float) || s.second_moments.size != n * sizeof(float))
 			throw std::runtime_error("Trainer: optimizer snapshot does not match the number of parameters");
 		HIP_CHECK(hipMemcpy(tm->m1, s.first_moments.data, s.first_moments.size, hipMemcpyHostToDevice));

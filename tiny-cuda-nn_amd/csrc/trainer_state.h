@@ -7,6 +7,7 @@
 
 #include "direct_exchange.h"
 #include "model_exec.h"
+#include "optimizer_chain.h"
 
 namespace tcnn_hip {
 
@@ -35,7 +36,16 @@ struct Trainer {
 	bool lr_decay = false;
 	float decay_base = 0.1f, lr_factor = 1.0f, base_lr = 0.0f;
 	uint32_t decay_interval = 10000, decay_start = 10000, decay_end = 10000000;
-	half_t* inference_params() const { return ema ? params_ema : params; }
+	// every other optimizer (SGD / Novograd bases, Lookahead / Average / Batched wrappers, in any chain): set instead of the fields above.
+	// The Adam-only fast paths -- the weight-gradient slabs summed inside Adam's launch, the step counters' representations,
+	// half_follows_master, the transposed copy kept current by the step -- belong to the fields above alone: a chain sees finished
+	// 16-bit gradients and leaves `params_t` stale.  Ranged stepping: OptimizerChain::ranged_refusal.
+	std::unique_ptr<OptimizerChain> chain;
+	half_t* inference_params() const {  // trainer.h:497-500: the optimizer's custom_weights() if it has any
+		if (chain) return chain->custom_weights() ? chain->custom_weights() : params;
+		return ema ? params_ema : params;
+	}
+	bool has_custom_weights() const { return chain ? chain->custom_weights() != nullptr : ema; }
 	// transposed copy of the network weights for the backward kernels; Adam keeps it current, anything else that writes
 	// `params` invalidates it
 	half_t* params_t = nullptr;
@@ -71,6 +81,7 @@ struct Trainer {
 	bool graph_capture = false;
 	hipGraphExec_t graph_exec = nullptr;
 	uint64_t graph_warm = ~0ull;
+	uint32_t graph_signature = 0;  // OptimizerChain::next_step_signature() of the step `graph_exec` was instantiated from
 	uint64_t graph_launches = 0, graph_instantiations = 0;
 	// data-parallel hosts: called between backward and the optimizer (tcnn_trainer_set_gradient_exchange)
 	void (*exchange)(void* user, void* gradients_fp16, size_t n_params, tcnn_stream_t stream) = nullptr;
@@ -128,6 +139,8 @@ void step_counters_to_counter_form(tcnn_trainable_model* tm, hipStream_t stream,
 void optimizer_step_ranges(tcnn_trainable_model* tm, hipStream_t stream, float loss_scale, size_t n_ranges, const size_t* begins, const size_t* ends,
                            bool advance, bool opens_profiled_step, bool profile_any_stage = false);
 void optimizer_step_all(tcnn_trainable_model* tm, hipStream_t stream, float loss_scale);  // one optimizer step over [0, n_params)
+// data-parallel schemes that step by parameter range: throws, naming the optimizer, if the trainer's cannot (Novograd, Lookahead, Average, Batched)
+void require_ranged_optimizer(const tcnn_trainable_model* tm, const char* scheme);
 // trainer_exchange.hip
 inline bool wants_ready_ranges(const tcnn_trainable_model* tm) { return tm->gradients_ready || tm->rccl_comm; }
 void notify_gradients_ready(tcnn_trainable_model* tm, hipStream_t stream, size_t begin, size_t end);

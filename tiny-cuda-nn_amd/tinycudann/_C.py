@@ -96,6 +96,12 @@ _sig("tcnn_optimizer_step_count", C.c_uint32, _vp)
 _sig("tcnn_optimizer_update_hyperparams", _i, _vp, C.c_char_p)
 _sig("tcnn_optimizer_state", _vp, _vp, _i)
 _sig("tcnn_optimizer_destroy", None, _vp)
+_sig("tcnn_optimizer_allocate_layers", _i, _vp, _sz, _sz, C.POINTER(_u32), C.POINTER(_u32))
+_sig("tcnn_optimizer_hyperparams_json", _cp, _vp)
+_sig("tcnn_optimizer_state_named", _i, _vp, _cp, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz))
+_sig("tcnn_optimizer_custom_weights", _vp, _vp)
+_sig("tcnn_optimizer_serialize", _i, _vp, _vp, _sz, C.POINTER(_sz))
+_sig("tcnn_optimizer_deserialize", _i, _vp, _cp, _sz)
 _sig("tcnn_loss_evaluate", _i, C.c_char_p, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _f, _vp, _vp, _vp, _vp, _vp)
 _sig("tcnn_create_network_with_input_encoding", _i, _u32, _u32, _cp, _cp, C.POINTER(_vp))
 _sig("tcnn_create_network", _i, _u32, _u32, _cp, C.POINTER(_vp))
@@ -164,6 +170,7 @@ _sig("tcnn_trainer_direct_status", _i, _vp, _vp, C.POINTER(_i))
 _sig("tcnn_trainer_direct_selftest", _i, _vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(_i))
 GRADIENT_READY_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p)  # (user, begin, end, stream)
 _sig("tcnn_trainer_optimizer_state", _vp, _vp, _i, C.POINTER(_i))
+_sig("tcnn_trainer_optimizer_state_named", _i, _vp, _cp, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz))
 _sig("tcnn_trainer_params_written", _i, _vp)
 _sig("tcnn_trainer_set_profiling", _i, _vp, _i, _i)
 _sig("tcnn_trainer_n_stages", _i)

@@ -33,16 +33,47 @@ class _DeviceView:
         self._owner = owner
 
 
-class Optimizer:
-    """Optimizer<T> on its own (optimizer.h:40-99; tcnn_create_optimizer): Adam over weight tensors the caller owns.  The first
-    n_matrix_weights parameters are matrix weights (weight decay / l2_reg apply to them, adam.h:79-110)."""
+def _named_state(call, handle, name, owner):
+    """a state buffer by its snapshot key without "_binary" as a zero-copy view: fp32 for 4-byte elements, the 16-bit type for 2-byte ones"""
+    ptr, count, elem = C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
+    _check(call(handle, name.encode(), C.byref(ptr), C.byref(count), C.byref(elem)))
+    if elem.value == 2:
+        return _half_tensor(ptr.value, count.value, owner)
+    return torch.as_tensor(_DeviceView(ptr.value, count.value, "<i4" if name == "param_steps" else "<f4", owner), device="cuda")
 
-    def __init__(self, config, n_weights, n_matrix_weights=0):
+
+class Optimizer:
+    """Optimizer<T> on its own (optimizer.h:40-99; tcnn_create_optimizer) over weight tensors the caller owns: any order of the wrappers
+    Ema, ExponentialDecay, Lookahead, Average, Batched (each at most once) around one base out of Adam, SGD, Novograd.  `layer_sizes`:
+    (rows, cols) of the weight matrices that lead the parameter vector (Adam's weight decay / l2_reg apply to them, adam.h:79-110; Novograd
+    steps them alone); `n_matrix_weights` alone means one such layer.  n_weights = 0 builds the optimizer without allocating anything."""
+
+    def __init__(self, config, n_weights, n_matrix_weights=0, layer_sizes=None):
         h = C.c_void_p()
         _check(_lib.tcnn_create_optimizer(json.dumps(config).encode(), C.byref(h)))
         self._h = h
         self.n = int(n_weights)
-        _check(_lib.tcnn_optimizer_allocate(h, self.n, int(n_matrix_weights)))
+        if layer_sizes is not None:
+            rows = (C.c_uint32 * len(layer_sizes))(*[int(r) for r, _ in layer_sizes])
+            cols = (C.c_uint32 * len(layer_sizes))(*[int(c) for _, c in layer_sizes])
+            _check(_lib.tcnn_optimizer_allocate_layers(h, self.n, len(layer_sizes), rows, cols))
+        elif self.n:
+            _check(_lib.tcnn_optimizer_allocate(h, self.n, int(n_matrix_weights)))
+
+    def hyperparams(self):
+        """Optimizer::hyperparams(): the reference's keys and otype spellings, nested optimizers under `nested`"""
+        return json.loads(_lib.tcnn_optimizer_hyperparams_json(self._h).decode())
+
+    def state_named(self, name):
+        """A state buffer by its snapshot key without "_binary" (weights_lookahead, weights_average, weights_samples, averaged_gradients,
+        averaged_gradients_half, first_moments, per_layer_second_moments, weights_ema, ...): a zero-copy view."""
+        return _named_state(_lib.tcnn_optimizer_state_named, self._h, name, self)
+
+    def custom_weights(self):
+        """Optimizer::custom_weights(): the outermost wrapper's inference weights (Ema's average, Lookahead's slow weights, Average's mean)
+        as a zero-copy view, or None."""
+        ptr = _lib.tcnn_optimizer_custom_weights(self._h)
+        return _half_tensor(ptr, self.n, self) if ptr else None
 
     def step(self, weights_full_precision, weights, gradients, loss_scale=128.0):
         """weights_full_precision fp32, weights / gradients in the library's 16-bit type (gradients scaled by loss_scale)."""
@@ -153,10 +184,17 @@ class TrainableModel:
     def optimizer_state(self):
         """(first_moments fp32, second_moments fp32, param_steps int32-viewed u32, steps_are_deficits) as zero-copy views of Adam's state."""
         flag = C.c_int(0)
-        m1 = self._tensor(_lib.tcnn_trainer_optimizer_state(self._h, 0, C.byref(flag)), "<f4")
+        first = _lib.tcnn_trainer_optimizer_state(self._h, 0, C.byref(flag))
+        if not first:  # the base optimizer is not Adam: optimizer_state_named()
+            _check(1)
+        m1 = self._tensor(first, "<f4")
         m2 = self._tensor(_lib.tcnn_trainer_optimizer_state(self._h, 1, None), "<f4")
         steps = self._tensor(_lib.tcnn_trainer_optimizer_state(self._h, 2, None), "<i4")
         return m1, m2, steps, bool(flag.value)
+
+    def optimizer_state_named(self, name):
+        """A state buffer of the trainer's optimizer by its snapshot key without "_binary" (tcnn_trainer_optimizer_state_named): a zero-copy view."""
+        return _named_state(_lib.tcnn_trainer_optimizer_state_named, self._h, name, self)
 
     def loss(self, ctx):
         v = C.c_float()
@@ -221,7 +259,8 @@ class TrainableModel:
 
     @property
     def params_inference(self):
-        """Trainer::params_inference (trainer.h:497-500): the EMA weights when the optimizer is wrapped in Ema, else `params`."""
+        """Trainer::params_inference (trainer.h:497-500): the optimizer's custom_weights() -- Ema's average, Lookahead's slow weights,
+        Average's mean, whichever wrapper is outermost -- else `params`."""
         return self._tensor(_lib.tcnn_trainer_params_inference(self._h), "<f2")
 
     @property
