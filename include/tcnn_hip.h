@@ -119,6 +119,18 @@ int tcnn_module_grid_indices(tcnn_module_t* m, tcnn_stream_t stream, uint32_t n_
 /* Grid layout accessors used by the reference's own known-answer test (tests/test_grid.cu:55-71). */
 int tcnn_module_grid_level_n_params(const tcnn_module_t* m, uint32_t level, size_t* out);
 int tcnn_module_grid_level_params_offset(const tcnn_module_t* m, uint32_t level, size_t* out);
+/* MultiLevelEncoding::set_max_level / max_level / set_max_level_gpu (multi_level_interface.h:101-123): coarse-to-fine control of a grid
+ * encoding.  With L levels, level l of a sample is switched off when l >= max_level * L + 1e-3 in the forward pass and when
+ * l > max_level * L + 1e-3 in the backward and second-order passes (the reference's two comparisons, sic): an off (sample, level) encodes
+ * to zeros, has zero dy_dx and contributes to no gradient.  _gpu: one fp32 max_level per sample in DEVICE memory, which then wins over the
+ * scalar; NULL clears it.  The array stays the caller's: it must hold at least n_elements floats at every later call on the module,
+ * forward, inference, backward and backward_backward_input alike (the backward passes of a context read the array its forward pass read),
+ * until it is cleared or replaced.  Run-time state: default 1.0 and no array, not among the hyperparameters, not serialized.
+ * Modules whose top-level encoding is a single grid only (a bare grid encoding of either precision, a NetworkWithInputEncoding over one);
+ * TCNN_ERROR_UNSUPPORTED with the encoding's name for every other module, a Composite with nested grids included. */
+int tcnn_module_set_max_level(tcnn_module_t* m, float value);
+int tcnn_module_max_level(const tcnn_module_t* m, float* out);
+int tcnn_module_set_max_level_gpu(tcnn_module_t* m, const float* device_ptr);
 /* Layout of a Composite encoding (composite.h; 0 nested encodings for every other module).  layout[0..3]: the first input dimension the
  * nested encoding reads, its input width, the first row of the (unreduced) encoded matrix it writes, its padded output width;
  * params[0..1]: where its parameters start behind the network's (if any) and how many it has. */
@@ -368,6 +380,12 @@ int tcnn_set_finalize_in_optimizer(int enable);
  * the reference's behaviour.  _stats: graph launches and instantiations so far. */
 int tcnn_trainer_set_graph_capture(tcnn_trainable_model_t* tm, int enable);
 int tcnn_trainer_graph_capture_stats(const tcnn_trainable_model_t* tm, uint64_t* launches, uint64_t* instantiations);
+/* The same three for a trainable model's grid encoding (see tcnn_module_set_max_level): they hold for training_step, forward / backward,
+ * tcnn_network_inference and their *_matrices forms from the next call on.  With graph capture on, the first training_step after either
+ * value changed runs plainly (outside the graph); later steps are captured again. */
+int tcnn_trainer_set_max_level(tcnn_trainable_model_t* tm, float value);
+int tcnn_trainer_max_level(const tcnn_trainable_model_t* tm, float* out);
+int tcnn_trainer_set_max_level_gpu(tcnn_trainable_model_t* tm, const float* device_ptr);
 /* Tuning knob: bytes of LDS one grid-backward workgroup uses for the table slice it owns (default 64 KiB). */
 int tcnn_trainer_set_lds_level_budget(tcnn_trainable_model_t* tm, uint32_t bytes);
 /* Grid backward formulation, process-wide: 0 = owner-computes LDS slices with fp32 accumulation on hashed levels,

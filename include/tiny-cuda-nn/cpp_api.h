@@ -131,10 +131,25 @@ public:
 	bool jit_fusion() const override { return tcnn_module_jit_fusion(m_) != 0; }
 	void set_jit_fusion(bool val) override { check(tcnn_module_set_jit_fusion(m_, val)); }
 
+	// MultiLevelEncoding::max_level / set_max_level / max_level_gpu / set_max_level_gpu (multi_level_interface.h:101-123) of a module whose
+	// encoding is a single grid; every other module throws.  The array stays the caller's device memory (see tcnn_module_set_max_level).
+	float max_level() const {
+		float v = 1.0f;
+		check(tcnn_module_max_level(m_, &v));
+		return v;
+	}
+	void set_max_level(float value) { check(tcnn_module_set_max_level(m_, value)); }
+	float* max_level_gpu() const { return m_max_level_gpu; }
+	void set_max_level_gpu(float* value) {
+		check(tcnn_module_set_max_level_gpu(m_, value));
+		m_max_level_gpu = value;
+	}
+
 	tcnn_module_t* c_handle() const { return m_; }
 
 private:
 	tcnn_module_t* m_;
+	float* m_max_level_gpu = nullptr;
 };
 
 // cpp_api.h:121-123 (the caller owns the result, as in the reference)

@@ -18,6 +18,31 @@ struct ModelHandle {
 };
 }  // namespace detail
 
+// The model's grid encoding as the callers of MultiLevelEncoding<T> see it (reference encodings/multi_level_interface.h:101-123): the
+// coarse-to-fine controls, under the reference's names.  max_level_gpu: one float per sample in device memory that stays the caller's and
+// holds at least batch-size entries at every later call; it wins over the scalar, nullptr clears it.  Run-time state, not serialized.
+// The library refuses (std::runtime_error) where the model's top-level encoding is not a single grid.
+template <typename T>
+class MultiLevelEncoding {
+public:
+	explicit MultiLevelEncoding(std::shared_ptr<detail::ModelHandle> h) : m_h(std::move(h)) {}
+	float max_level() const {
+		float v = 1.0f;
+		check(tcnn_trainer_max_level(m_h->tm, &v));
+		return v;
+	}
+	void set_max_level(float value) { check(tcnn_trainer_set_max_level(m_h->tm, value)); }
+	float* max_level_gpu() const { return m_max_level_gpu; }
+	void set_max_level_gpu(float* value) {
+		check(tcnn_trainer_set_max_level_gpu(m_h->tm, value));
+		m_max_level_gpu = value;
+	}
+
+private:
+	std::shared_ptr<detail::ModelHandle> m_h;
+	float* m_max_level_gpu = nullptr;
+};
+
 template <typename T>
 class NetworkWithInputEncoding {
 public:
@@ -52,7 +77,17 @@ public:
 	bool jit_fusion() const { return false; }  // no RTC path in this build (north_star); the statically fused kernels always run
 	void set_jit_fusion(bool) {}
 
-	void bind(std::shared_ptr<detail::ModelHandle> h) { m_h = std::move(h); }  // called by Trainer
+	// network_with_input_encoding.h:196: the encoding, for what callers do with it -- dynamic_cast<MultiLevelEncoding<T>*>(...)->set_max_level(...)
+	const std::shared_ptr<MultiLevelEncoding<T>>& encoding() {
+		handle();
+		if (!m_multi_level) m_multi_level = std::make_shared<MultiLevelEncoding<T>>(m_h);
+		return m_multi_level;
+	}
+
+	void bind(std::shared_ptr<detail::ModelHandle> h) {  // called by Trainer
+		m_h = std::move(h);
+		m_multi_level.reset();
+	}
 
 private:
 	tcnn_trainable_model_t* handle() const {
@@ -62,6 +97,7 @@ private:
 	uint32_t m_n_input_dims, m_n_output_dims;
 	json m_encoding, m_network;
 	std::shared_ptr<detail::ModelHandle> m_h;
+	std::shared_ptr<MultiLevelEncoding<T>> m_multi_level;
 };
 
 }  // namespace tcnn

@@ -162,6 +162,9 @@ int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_,
 		}
 	}
 	GridIO io = {input, md.n_input_dims, 1u, n, 1u, e.padded_output_width};  // the bare encoding's output is sample-major (cpp_api.cu:94-95)
+	io.max_level = ctx->ctx.max_level_gpu;  // max_level as the forward pass of this context saw it
+	GridMeta grid = e.grid;
+	grid.max_level = ctx->ctx.max_level;
 	io.ddx = dL_ddLdinput;
 	io.ddx_stride_i = md.n_input_dims;
 	io.ddx_stride_d = 1u;
@@ -175,7 +178,7 @@ int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_,
 	}
 	if (dL_dparams && e.n_params > 0) {  // grid.h:942-975, GradientMode::Overwrite
 		uint32_t budget = m->lds_level_budget ? m->lds_level_budget : g_default_lds_slice_bytes;
-		GridBackwardWorkspace ws = grid_backward_workspace_size(e.grid, n, GridBackwardMode::Bucketed, budget);
+		GridBackwardWorkspace ws = grid_backward_workspace_size(grid, n, GridBackwardMode::Bucketed, budget);
 		Scratch queues;
 		if (ws.scratch_bytes) {
 			queues = Scratch(stream, ws.scratch_bytes);
@@ -183,10 +186,10 @@ int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_,
 			ws.scratch_bytes = queues.bytes;
 			ws.counters = ZeroedCounters::get(stream, ws.n_counters);
 		}
-		grid_backward(stream, e.grid, io, (const half_t*)dL_doutput, (half_t*)dL_dparams, false, GridBackwardMode::Bucketed, budget, ws);
+		grid_backward(stream, grid, io, (const half_t*)dL_doutput, (half_t*)dL_dparams, false, GridBackwardMode::Bucketed, budget, ws);
 	}
 	if (dL_dinput) {  // grid.h:977-1010
-		grid_backward_backward_input(stream, e.grid, io, (const half_t*)dL_doutput, (const half_t*)params, dL_dinput, md.n_input_dims, 1u);
+		grid_backward_backward_input(stream, grid, io, (const half_t*)dL_doutput, (const half_t*)params, dL_dinput, md.n_input_dims, 1u);
 	}
 	if (m->fp32_io) {  // dL_ddLdoutput does not depend on dL_doutput; the other two carry its scale
 		if (dL_ddLdoutput_f32) cast_f16_to_f32(stream, n_out_elems, ddy16.as<half_t>(), (float*)dL_ddLdoutput_f32);
@@ -239,6 +242,28 @@ int tcnn_module_grid_level_params_offset(const tcnn_module_t* m, uint32_t level,
 	TCNN_API_BEGIN
 	if (!m->md.enc.is_grid() || level >= m->md.enc.grid.n_levels) throw std::runtime_error("grid_level_params_offset: invalid level");
 	*out = m->md.enc.grid.offset[level];
+	TCNN_API_END
+}
+// MultiLevelEncoding::set_max_level / max_level / set_max_level_gpu (multi_level_interface.h:101-123): run-time state of a lone grid
+int tcnn_module_set_max_level(tcnn_module_t* m, float value) {
+	TCNN_API_BEGIN
+	if (!m) throw std::runtime_error("tcnn_module_set_max_level: null module");
+	if (const int r = refuse_max_level(m->md)) return r;
+	m->md.enc.grid.max_level = value;
+	TCNN_API_END
+}
+int tcnn_module_max_level(const tcnn_module_t* m, float* out) {
+	TCNN_API_BEGIN
+	if (!m || !out) throw std::runtime_error("tcnn_module_max_level: null argument");
+	if (const int r = refuse_max_level(m->md)) return r;
+	*out = m->md.enc.grid.max_level;
+	TCNN_API_END
+}
+int tcnn_module_set_max_level_gpu(tcnn_module_t* m, const float* device_ptr) {
+	TCNN_API_BEGIN
+	if (!m) throw std::runtime_error("tcnn_module_set_max_level_gpu: null module");
+	if (const int r = refuse_max_level(m->md)) return r;
+	m->md.enc.max_level_gpu = device_ptr;
 	TCNN_API_END
 }
 uint32_t tcnn_module_n_nested(const tcnn_module_t* m) { return (uint32_t)m->md.enc.nested.size(); }

@@ -220,6 +220,7 @@ static int training_step_fused(tcnn_trainable_model_t* tm, hipStream_t stream, c
 	ForwardCtx& fc = c->model_ctx;
 	fc.stream = stream;
 	fc.n = n;
+	fc.keep_max_level(md.enc);
 	const uint32_t padded = md.padded_output_width();
 	const bool want_grads = gradient_mode != TCNN_GRADIENT_IGNORE;
 	const bool accumulate = gradient_mode == TCNN_GRADIENT_ACCUMULATE;
@@ -312,7 +313,7 @@ static int training_step_fused_captured(tcnn_trainable_model_t* tm, tcnn_stream_
                                         const void* external_dL_dy, tcnn_train_context_t** ctx, bool context_wanted) {
 	const uint64_t shape = (uint64_t)n | ((uint64_t)(dL_dinput != nullptr) << 32) | ((uint64_t)(gradient_mode & 3) << 33) | ((uint64_t)(use_inference_params != 0) << 35) |
 	                       ((uint64_t)(external_dL_dy != nullptr) << 36) | ((uint64_t)context_wanted << 37) | ((uint64_t)(run_optimizer != 0) << 38) |
-	                       ((uint64_t)(data_pdf != nullptr) << 39);
+	                       ((uint64_t)(data_pdf != nullptr) << 39) | ((uint64_t)(tm->max_level_generation & 0xFFFFFFu) << 40);
 	bool capture = tm->graph_capture && stream != nullptr && !tm->profiler && !tm->exchange && !tm->direct.active() && !wants_ready_ranges(tm) && n > 0 &&
 	               tm->graph_warm == shape && (debug_launch_flags() & 1) == 0;
 	if (capture) {
@@ -648,6 +649,32 @@ int tcnn_trainer_get_stage_times(tcnn_trainable_model_t* tm, double* total_ms, u
 int tcnn_trainer_set_lds_level_budget(tcnn_trainable_model_t* tm, uint32_t bytes) {
 	tm->lds_level_budget = bytes;
 	return TCNN_OK;
+}
+
+// MultiLevelEncoding::set_max_level / max_level / set_max_level_gpu for the trainer's model.  A change takes effect at the next pass; with
+// graph capture on, the first training_step after a change runs outside the graph (max_level_generation is part of the step's shape).
+int tcnn_trainer_set_max_level(tcnn_trainable_model_t* tm, float value) {
+	TCNN_API_BEGIN
+	if (!tm) throw std::runtime_error("tcnn_trainer_set_max_level: null model");
+	if (const int r = refuse_max_level(tm->md)) return r;
+	if (tm->md.enc.grid.max_level != value) ++tm->max_level_generation;
+	tm->md.enc.grid.max_level = value;
+	TCNN_API_END
+}
+int tcnn_trainer_max_level(const tcnn_trainable_model_t* tm, float* out) {
+	TCNN_API_BEGIN
+	if (!tm || !out) throw std::runtime_error("tcnn_trainer_max_level: null argument");
+	if (const int r = refuse_max_level(tm->md)) return r;
+	*out = tm->md.enc.grid.max_level;
+	TCNN_API_END
+}
+int tcnn_trainer_set_max_level_gpu(tcnn_trainable_model_t* tm, const float* device_ptr) {
+	TCNN_API_BEGIN
+	if (!tm) throw std::runtime_error("tcnn_trainer_set_max_level_gpu: null model");
+	if (const int r = refuse_max_level(tm->md)) return r;
+	if (tm->md.enc.max_level_gpu != device_ptr) ++tm->max_level_generation;
+	tm->md.enc.max_level_gpu = device_ptr;
+	TCNN_API_END
 }
 
 int tcnn_trainer_set_graph_capture(tcnn_trainable_model_t* tm, int enable) {

@@ -28,7 +28,7 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_backward_atomic(const Gri
                                                                         half_t* __restrict__ grid_gradient) {
 	uint32_t level, tile;
 	if (!grid_work_item(meta.n_levels, div_round_up(io.n, GRID_TILE), level, tile)) return;
-	if (level_is_off<false>(meta, level, F)) return;
+	if (!io.max_level && level_is_off<false>(meta, level, F)) return;
 	const Level<D> lv = make_level<D>(meta, level);
 	half_t* __restrict__ grad = grid_gradient + (size_t)meta.offset[level] * F;
 	const bool second_order = io.ddx != nullptr;  // kernel_grid_backward_input_backward_grid (grid.h:427-455): another corner weight
@@ -36,6 +36,7 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_backward_atomic(const Gri
 	for (uint32_t s = 0; s < GRID_SPT; ++s) {
 		const uint32_t i = tile * GRID_TILE + s * GRID_THREADS + threadIdx.x;
 		if (i >= io.n) continue;
+		if (io.max_level && level_is_off<false>(meta, io, i, level, F)) continue;
 		Cell<D> c = make_cell<D, false>(lv, io, i);
 		half_t g[F];
 #pragma unroll
@@ -69,12 +70,13 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_backward_atomic_f32(const
                                                                             float* __restrict__ grid_gradient) {
 	uint32_t level, tile;
 	if (!grid_work_item(meta.n_levels, div_round_up(io.n, GRID_TILE), level, tile)) return;
-	if (level_is_off<false>(meta, level, F)) return;
+	if (!io.max_level && level_is_off<false>(meta, level, F)) return;
 	const Level<D> lv = make_level<D>(meta, level);
 	float* __restrict__ grad = grid_gradient + (size_t)meta.offset[level] * F;
 	for (uint32_t s = 0; s < GRID_SPT; ++s) {
 		const uint32_t i = tile * GRID_TILE + s * GRID_THREADS + threadIdx.x;
 		if (i >= io.n) continue;
+		if (io.max_level && level_is_off<false>(meta, io, i, level, F)) continue;
 		Cell<D> c = make_cell<D, false>(lv, io, i);
 		float g[F];
 #pragma unroll
@@ -112,7 +114,7 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_backward_atomic_f32(const
 enum class Acc { F32, PK16, FIX64 };
 
 template <uint32_t D, uint32_t F, Acc ACC, bool FAST>
-TCNN_DEVICE void sliced_accumulate(const Level<D>& lv, const GridIO& io, const half_t* __restrict__ dL_dy, uint32_t level, uint32_t begin,
+TCNN_DEVICE void sliced_accumulate(const GridMeta& meta, const Level<D>& lv, const GridIO& io, const half_t* __restrict__ dL_dy, uint32_t level, uint32_t begin,
                                    uint32_t end, uint32_t slice_begin, uint32_t slice_count, unsigned char* lds_raw) {
 	constexpr uint32_t N_CORNERS = 1u << D;
 	float* tab_f = (float*)lds_raw;                            // [entries][F]
@@ -143,6 +145,7 @@ TCNN_DEVICE void sliced_accumulate(const Level<D>& lv, const GridIO& io, const h
 			}
 			if (lv.nearest) match &= 1u;
 			if (base + u * SLICED_THREADS >= end) match = 0;
+			if (io.max_level && level_is_off<false>(meta, io, min(base + u * SLICED_THREADS, end - 1), level, F)) match = 0;  // per-sample max_level
 
 			while (match) {
 				const uint32_t idx = (uint32_t)__builtin_ctz(match);
@@ -189,9 +192,9 @@ TCNN_DEVICE void sliced_level(const GridMeta& meta, const GridIO& io, const Leve
 		const uint32_t begin = chunk * per_chunk;
 		const uint32_t end = min(begin + per_chunk, io.n);
 		if (lv.fast) {
-			sliced_accumulate<D, F, ACC, true>(lv, io, dL_dy, level, begin, end, slice_begin, slice_count, lds_raw);
+			sliced_accumulate<D, F, ACC, true>(meta, lv, io, dL_dy, level, begin, end, slice_begin, slice_count, lds_raw);
 		} else {
-			sliced_accumulate<D, F, ACC, false>(lv, io, dL_dy, level, begin, end, slice_begin, slice_count, lds_raw);
+			sliced_accumulate<D, F, ACC, false>(meta, lv, io, dL_dy, level, begin, end, slice_begin, slice_count, lds_raw);
 		}
 	}
 	__syncthreads();
@@ -236,7 +239,7 @@ __global__ void __launch_bounds__(SLICED_THREADS) k_grid_backward_sliced(const G
 	const uint32_t n_chunks = (plan.block_begin[item + 1] - plan.block_begin[item]) / n_slices;
 	const uint32_t slice = local_block % n_slices, chunk = local_block / n_slices;
 
-	const bool level_off = level_is_off<false>(meta, level, F);
+	const bool level_off = !io.max_level && level_is_off<false>(meta, level, F);  // (a per-sample max_level is tested sample by sample)
 	const Level<D> lv = make_level<D>(meta, level);
 
 	if (kind == SLICE_BUCKET) {
@@ -256,6 +259,7 @@ __global__ void __launch_bounds__(SLICED_THREADS) k_grid_backward_sliced(const G
 		const uint32_t per_tile = div_round_up(io.n, n_slices);
 		const uint32_t begin = slice * per_tile, end = min(begin + per_tile, io.n);
 		for (uint32_t i = begin + threadIdx.x; i < end; i += SLICED_THREADS) {
+			if (io.max_level && level_is_off<false>(meta, io, i, level, F)) continue;
 			const Cell<D> c = make_cell<D, false>(lv, io, i);
 			half_t g[F];
 #pragma unroll

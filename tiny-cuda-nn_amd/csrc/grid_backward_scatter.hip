@@ -48,7 +48,8 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 	// persistent workgroup: `wgs_per_level` of them share the sample tiles of one level
 	const uint32_t j = blockIdx.x / plan.wgs_per_level, first_tile = blockIdx.x % plan.wgs_per_level;
 	const uint32_t level = plan.level[j], nb = plan.n_buckets[j], shift = plan.shift;
-	if (level_is_off<false>(meta, level, F)) return;  // no records, the owners store zeros
+	const bool per_sample = io.max_level != nullptr;
+	if (!per_sample && level_is_off<false>(meta, level, F)) return;  // no records, the owners store zeros
 	const Level<D> lv = make_level<D>(meta, level);
 
 	// Queue unit: a PAIR of records -- the two corners that differ in dimension 0 only.  Their table entries are
@@ -113,12 +114,20 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 			for (uint32_t f = 0; f < F; ++f) m = __builtin_fmaxf(m, __builtin_fabsf((float)g[s][f]));
 			return m;
 		};
+		// a per-sample max_level: bit s = sample s of this lane is off for the level -- it emits no record (and adds nothing to the level's sum)
+		uint32_t off_mask = 0u;
+		if (!SECOND_ORDER && per_sample) {  // (the second-order instance tests inside derive(), next to its ddx loads: no mask to keep alive)
+#pragma unroll
+			for (uint32_t s = 0; s < SPT; ++s) {
+				if (level_is_off<false>(meta, io, min(tile * TILE + s * BUCKET_THREADS + threadIdx.x, io.n - 1u), level, F)) off_mask |= 1u << s;
+			}
+		}
 		// first order: the corner weights of a sample add up to one, so the sum of |dL/dy| over the workgroup's tiles is the sum of what is
 		// emitted.  (The second-order pass gathers its sum inside derive() below, where the weights are known.)
 		if constexpr (HALF_IS_BF16 && !second_order) {
 #pragma unroll
 			for (uint32_t s = 0; s < SPT; ++s) {
-				if (tile * TILE + s * BUCKET_THREADS + threadIdx.x < io.n) level_abs_sum += __builtin_fminf(max_abs_dy(s), LEVEL_SUM_CLAMP);  // (NaN -> the other operand: the bound test sees it)
+				if (tile * TILE + s * BUCKET_THREADS + threadIdx.x < io.n && !((off_mask >> s) & 1u)) level_abs_sum += __builtin_fminf(max_abs_dy(s), LEVEL_SUM_CLAMP);  // (NaN -> the other operand: the bound test sees it)
 			}
 		}
 		// ---- derive the records of my samples; rank each pair within its bucket
@@ -127,7 +136,10 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 			constexpr bool FAST = decltype(fast_tag)::value;
 #pragma unroll
 			for (uint32_t s = 0; s < SPT; ++s) {
-				const bool valid = tile * TILE + s * BUCKET_THREADS + threadIdx.x < io.n;
+				bool valid = tile * TILE + s * BUCKET_THREADS + threadIdx.x < io.n && !((off_mask >> s) & 1u);
+				if constexpr (second_order) {
+					if (per_sample && level_is_off<false>(meta, io, min(tile * TILE + s * BUCKET_THREADS + threadIdx.x, io.n - 1u), level, F)) valid = false;
+				}
 				const Cell<D> c = make_cell<D, FAST>(lv, x[s]);
 				float dd[D];
 #pragma unroll

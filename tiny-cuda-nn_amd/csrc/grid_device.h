@@ -232,10 +232,20 @@ TCNN_DEVICE void load_features(const half_t* p, h2 (&v)[(F + 1) / 2]) {
 // Is `level` switched off by max_level (MultiLevelEncoding::m_max_level)?  The reference tests '>=' in the forward pass (grid.h:75,
 // INCLUSIVE) and '>' in the backward passes (grid.h:242, 483) -- sic, both are restated; the float expression is grid.h:72's, as written.
 template <bool INCLUSIVE>
-TCNN_DEVICE bool level_is_off(const GridMeta& meta, uint32_t level, uint32_t F) {
+TCNN_HOST_DEVICE bool level_is_off(const GridMeta& meta, float max_level_value, uint32_t level, uint32_t F) {
 	const uint32_t n_features = meta.n_levels * F;
-	const float max_level = (meta.max_level * (float)n_features) / (float)F;
+	const float max_level = (max_level_value * (float)n_features) / (float)F;
 	return INCLUSIVE ? (float)level >= max_level + 1e-3f : (float)level > max_level + 1e-3f;
+}
+template <bool INCLUSIVE>
+TCNN_HOST_DEVICE bool level_is_off(const GridMeta& meta, uint32_t level, uint32_t F) {
+	return level_is_off<INCLUSIVE>(meta, meta.max_level, level, F);
+}
+// The per-sample form (set_max_level_gpu, grid.h:70-72: the array wins over the scalar): is `level` off for sample i?  Only where
+// io.max_level is set -- the kernels test that pointer once, wave-uniformly, and keep the scalar's per-level answer otherwise.
+template <bool INCLUSIVE>
+TCNN_DEVICE bool level_is_off(const GridMeta& meta, const GridIO& io, uint32_t i, uint32_t level, uint32_t F) {
+	return level_is_off<INCLUSIVE>(meta, io.max_level[i], level, F);
 }
 
 // Calls fn(D, F), two std::integral_constants, for the encoding's dimensions and features per level: every launcher instantiates its

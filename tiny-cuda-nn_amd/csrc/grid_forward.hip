@@ -94,12 +94,12 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_forward(const GridMeta me
 #pragma unroll
 		for (uint32_t s = 0; s < GRID_SPT; ++s) {
 			const uint32_t i = tile * GRID_TILE + s * GRID_THREADS + threadIdx.x;
-			if (i < io.n) grid_forward_sample<D, F, DYDX, true>(lv, io, grid, level, i, level_off, out, dy_dx);
+			if (i < io.n) grid_forward_sample<D, F, DYDX, true>(lv, io, grid, level, i, io.max_level ? level_is_off<true>(meta, io, i, level, F) : level_off, out, dy_dx);
 		}
 	} else {
 		for (uint32_t s = 0; s < GRID_SPT; ++s) {
 			const uint32_t i = tile * GRID_TILE + s * GRID_THREADS + threadIdx.x;
-			if (i < io.n) grid_forward_sample<D, F, DYDX, false>(lv, io, grid, level, i, level_off, out, dy_dx);
+			if (i < io.n) grid_forward_sample<D, F, DYDX, false>(lv, io, grid, level, i, io.max_level ? level_is_off<true>(meta, io, i, level, F) : level_off, out, dy_dx);
 		}
 	}
 }
@@ -193,9 +193,9 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_forward_tiles(const GridM
 		for (uint32_t k = 0; k < FWD_SEGMENTS_AT_ONCE; ++k) head[k] = plan.segments[xcd][k];
 #if !defined(TCNN_HOST_EMU)
 		{  // (all of it now, in ONE round -- the four segments and what the position loads need of the other kernel arguments)
-			uint64_t positions = (uint64_t)(uintptr_t)io.positions;
+			uint64_t positions = (uint64_t)(uintptr_t)io.positions, per_sample = (uint64_t)(uintptr_t)io.max_level;
 			uint32_t a = io.pos_stride_i, b = io.pos_stride_d, c = io.n, d = meta.grid_type, e = meta.interp;
-			asm volatile("" : "+s"(positions), "+s"(a), "+s"(b), "+s"(c), "+s"(d), "+s"(e), "+s"(head[0].level), "+s"(head[0].tile_begin), "+s"(head[0].tile_end),
+			asm volatile("" : "+s"(positions), "+s"(per_sample), "+s"(a), "+s"(b), "+s"(c), "+s"(d), "+s"(e), "+s"(head[0].level), "+s"(head[0].tile_begin), "+s"(head[0].tile_end),
 			             "+s"(head[0].hashmap_size), "+s"(head[0].resolution), "+s"(head[0].scale_bits), "+s"(head[0].offset), "+s"(head[0].fast));
 #pragma unroll
 			for (uint32_t k = 1; k < FWD_SEGMENTS_AT_ONCE; ++k) {
@@ -243,10 +243,12 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_forward_tiles(const GridM
 	const Level<D> lv = level_of_segment<D>(meta, mine);
 	const half_t* __restrict__ grid = params + (size_t)mine.offset * F;
 	const bool level_off = level_is_off<true>(meta, level, F);
-	if (level_off || lv.nearest) {  // rare forms: one sample at a time
+	if (level_off || lv.nearest || io.max_level) {  // rare forms: one sample at a time
+		// (a per-sample max_level: the lane's value is read ahead of its table loads; an off lane issues none, a wave of off lanes
+		// branches over the gather and only stores its zeros)
 		for (uint32_t s = 0; s < SPT; ++s) {
 			const uint32_t i = first + s * GRID_THREADS + threadIdx.x;
-			if (i < io.n) grid_forward_sample<D, F, false, false>(lv, io, grid, level, i, level_off, out, nullptr);
+			if (i < io.n) grid_forward_sample<D, F, false, false>(lv, io, grid, level, i, io.max_level ? level_is_off<true>(meta, io, i, level, F) : level_off, out, nullptr);
 		}
 	} else if (lv.fast) {  // wave-uniform: one lean code path per level kind
 		grid_forward_tile<D, F, SPT, true>(lv, io, grid, level, first, x, out);
@@ -274,6 +276,7 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_forward_f32(const GridMet
 	for (uint32_t s = 0; s < GRID_SPT; ++s) {
 		const uint32_t i = tile * GRID_TILE + s * GRID_THREADS + threadIdx.x;
 		if (i >= io.n) continue;
+		const bool off = io.max_level ? level_is_off<true>(meta, io, i, level, F) : level_off;
 		float result[F], grads[DYDX ? F : 1][D];
 #pragma unroll
 		for (uint32_t f = 0; f < F; ++f) result[f] = 0.0f;
@@ -281,7 +284,7 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_forward_f32(const GridMet
 		for (uint32_t f = 0; f < (DYDX ? F : 1); ++f)
 #pragma unroll
 			for (uint32_t d = 0; d < D; ++d) grads[f][d] = 0.0f;
-		if (!level_off) {
+		if (!off) {
 			const Cell<D> c = make_cell<D, false>(lv, io, i);
 			if (lv.nearest) {
 				const float* v = grid + (size_t)corner_index<D, false>(lv, c, 0) * F;
@@ -363,6 +366,10 @@ static ForwardPlan make_forward_plan(const GridMeta& meta, uint32_t n, uint32_t 
 			                    : hashed ? 8.0 * (1.0 + 2.5 * miss)
 			                             : (4.6 + 1.15 * std::log2(in_l2 / (24.0 * 1024.0))) * (1.0 + 0.8 * miss);
 			cost[l] = uniform ? 16u : (uint32_t)(4.0 * base + 0.5);  // (quarter-microsecond units: the cuts fall on whole tiles)
+			// A level the scalar max_level switches off gathers nothing: its items load positions and store zeros.  Weighed like the others they
+			// left the levels that are still on -- the coarse ones, all in the first XCDs' runs -- where they were, and the forward pass took as
+			// long as with every level on (measured: 0.082 ms at max_level 1.0, 0.5 and 0.25 alike).  A quarter of the cheapest kind.
+			if (!uniform && level_is_off<true>(meta, l, meta.n_feat)) cost[l] = 4u;
 			total += (uint64_t)cost[l] * plan.tiles;
 		}
 		bool ok = true;

@@ -44,6 +44,8 @@ struct GridIO {
 	// second-order pass only: dL/d(dL_dx), element (dim d, sample i) at ddx[i * ddx_stride_i + d * ddx_stride_d]
 	const float* ddx = nullptr;
 	uint32_t ddx_stride_i = 0, ddx_stride_d = 0;
+	// per-sample max_level (MultiLevelEncoding::set_max_level_gpu): max_level[i] replaces GridMeta::max_level for sample i; null: the scalar holds
+	const float* max_level = nullptr;
 };
 
 // Forward: writes n_levels*F features (padding columns are the caller's job). dy_dx may be null;

@@ -54,8 +54,9 @@ __global__ void __launch_bounds__(128) k_grid_backward_backward_input(const Grid
 #pragma unroll
 	for (uint32_t d = 0; d < D; ++d) out[d] = 0.0f;
 	const bool nearest = meta.interp == (uint32_t)InterpolationType::Nearest;
+	const float max_level = io.max_level ? io.max_level[i] : meta.max_level;  // per sample where the array is set (it wins, grid.h:70-72)
 	for (uint32_t level = 0; level < meta.n_levels && !nearest; ++level) {
-		if (level_is_off<false>(meta, level, F)) break;
+		if (level_is_off<false>(meta, max_level, level, F)) break;
 		const Level<D> lv = make_level<D>(meta, level);
 		const half_t* __restrict__ grid = params + (size_t)meta.offset[level] * F;
 		const Cell<D> c = make_cell<D, false>(lv, x);

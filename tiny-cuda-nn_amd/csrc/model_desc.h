@@ -45,6 +45,9 @@ struct EncodingDesc {
 	// the top-level encoding is a single grid: what level groups, the LDS budget, grid_level_* / grid_indices, second-order gradients
 	// and the optimizer's per-level deficits apply to.  Grids nested in a Composite take the plain path.
 	bool is_grid() const { return kind == EncodingKind::Grid; }
+	// Run-time state of such a grid, as in the reference (multi_level_interface.h:101-123): not a hyperparameter, not serialized.  The scalar
+	// lives in grid.max_level; the array is the CALLER'S device memory, one float per sample of every later call, and wins over the scalar.
+	const float* max_level_gpu = nullptr;
 	bool is_composite() const { return kind == EncodingKind::Composite; }
 	bool has_nested_grid() const;
 	uint32_t unreduced_width() const { return reduction == ReductionType::Concatenation ? padded_output_width : padded_output_width * (uint32_t)nested.size(); }
@@ -76,6 +79,13 @@ struct Model {
 	uint32_t padded_output_width() const { return has_network ? net.mlp.padded_out : enc.padded_output_width; }
 	uint32_t output_width() const { return has_network ? net.n_output_dims : enc.padded_output_width; }
 	std::string name() const { return has_network ? "NetworkWithInputEncoding" : enc.name(); }
+
+	// set_max_level / set_max_level_gpu apply where the top-level encoding is a single grid: why they do not apply here (empty: they do)
+	std::string max_level_refusal() const {
+		if (enc.is_grid()) return "";
+		return std::string("set_max_level: ") + enc.name() + " is not a multi-level grid encoding" +
+		       (enc.is_composite() ? " (grids nested in a CompositeEncoding take the plain path: max_level does not reach them)" : "");
+	}
 
 	void finish();  // fills hyper_json
 	// network_with_input_encoding.h:124-130 + fully_fused_mlp.cu:868-893 + grid.h:1076-1079

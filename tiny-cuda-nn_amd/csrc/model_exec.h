@@ -29,6 +29,14 @@ struct ForwardCtx {
 	// type and layout of the pass's output with unreduced_width() rows; one dy_dx per nested encoding (allocated for the grids)
 	Scratch unreduced;
 	std::vector<Scratch> nested_dy_dx;
+	// a lone grid's max_level state as the forward pass that filled this context read it: the backward and second-order passes of the context
+	// run with these, whatever the setters have been told since (EncodingDesc::max_level_gpu says whose memory the array is)
+	float max_level = 1.0f;
+	const float* max_level_gpu = nullptr;
+	void keep_max_level(const EncodingDesc& e) {
+		max_level = e.grid.max_level;
+		max_level_gpu = e.max_level_gpu;
+	}
 };
 
 // The grid's parameter gradients in groups of consecutive levels, each reported as soon as its kernels are enqueued (data-parallel
@@ -39,6 +47,9 @@ struct LevelGroups {
 	void (*ready)(void* ctx, size_t begin, size_t end) = nullptr;
 	void* ctx = nullptr;
 };
+// The C ABI's max_level entry points (api_module.hip, api_trainer.hip): TCNN_OK where `md` has a lone top-level grid, otherwise the last error
+// is set to Model::max_level_refusal() and TCNN_ERROR_UNSUPPORTED comes back
+int refuse_max_level(const Model& md);
 void check_batch(uint32_t n, uint32_t widest = 128);
 uint32_t widest_matrix(const Model& md);  // the widest matrix any pass over `md` indexes, in elements per sample
 // Encoding forward into a feature-major (SoA) or sample-major (AoS) half matrix.  dy_dx: a lone grid's; a Composite keeps what its backward

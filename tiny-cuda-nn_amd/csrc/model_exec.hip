@@ -9,6 +9,13 @@
 
 namespace tcnn_hip {
 
+int refuse_max_level(const Model& md) {
+	const std::string why = md.max_level_refusal();
+	if (why.empty()) return TCNN_OK;
+	set_last_error(why);
+	return TCNN_ERROR_UNSUPPORTED;
+}
+
 void check_batch(uint32_t n, uint32_t widest) {
 	if (n % BATCH_SIZE_GRANULARITY != 0) {  // object.h:170, 217, 298
 		throw std::runtime_error("Batch size " + std::to_string(n) + " must be a multiple of " + std::to_string(BATCH_SIZE_GRANULARITY) + ".");
@@ -168,6 +175,7 @@ void encoding_forward(hipStream_t stream, Profiler* profiler, const Model& md, c
 		composite_forward(stream, e, layout, n, input, enc_params, out, stride_k, stride_i, ctx, prepare_input_gradients);
 	} else if (e.is_grid()) {
 		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
+		io.max_level = e.max_level_gpu;
 		grid_forward(stream, e.grid, io, enc_params, out, dy_dx);
 		const uint32_t n_to_pad = e.padded_output_width - e.n_output_dims;
 		if (n_to_pad > 0) {  // grid.h:757-766: padded dims are zero
@@ -193,6 +201,7 @@ void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, cons
 	if (ctx) {
 		ctx->stream = stream;
 		ctx->n = n;
+		ctx->keep_max_level(md.enc);
 	}
 	float* dy_dx = nullptr;
 	if (ctx && prepare_input_gradients && md.enc.is_grid()) {
@@ -406,6 +415,9 @@ void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, 
 		}
 	} else if (e.is_grid()) {
 		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
+		io.max_level = ctx.max_level_gpu;  // max_level as the forward pass of this context saw it
+		GridMeta grid = e.grid;
+		grid.max_level = ctx.max_level;
 		if (want_grads && e.n_params > 0) {
 			half_t* grid_grads = dL_dparams + md.n_mlp_params();
 			// Overwrite vs Accumulate (grid.h:865-867) is handled inside: the owner-computes kernel stores
@@ -414,17 +426,17 @@ void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, 
 			if (lds_level_budget == 0) lds_level_budget = g_default_lds_slice_bytes;
 			// level groups: only where a level's treatment does not depend on its index among ALL levels (every level switched on,
 			// no per-level random stream) and nothing else rides on the pass
-			const uint32_t L = e.grid.n_levels, F = e.grid.n_feat;
+			const uint32_t L = grid.n_levels, F = grid.n_feat;
 			uint32_t n_groups = groups ? std::min(std::max(groups->n_groups, 1u), L) : 1u;
-			if (e.grid.max_level < 1.0f || e.grid.stochastic != 0u) n_groups = 1;
-			const std::vector<std::pair<uint32_t, uint32_t>> level_ranges = split_levels(e.grid, n_groups);
+			if (grid.max_level < 1.0f || io.max_level || grid.stochastic != 0u) n_groups = 1;
+			const std::vector<std::pair<uint32_t, uint32_t>> level_ranges = split_levels(grid, n_groups);
 			// one workspace for all groups: the largest any of them asks for (a group of later levels can bucket levels that the plan of
 			// the whole grid, which takes the first MAX_BUCKET_LEVELS eligible ones, left to the other kinds)
-			GridBackwardWorkspace ws = grid_backward_workspace_size(e.grid, n, mode, lds_level_budget);
+			GridBackwardWorkspace ws = grid_backward_workspace_size(grid, n, mode, lds_level_budget);
 			if (level_ranges.size() > 1) {
 				ws = GridBackwardWorkspace();
 				for (const auto& r : level_ranges) {
-					const GridBackwardWorkspace w = grid_backward_workspace_size(grid_levels(e.grid, r.first, r.second), n, mode, lds_level_budget);
+					const GridBackwardWorkspace w = grid_backward_workspace_size(grid_levels(grid, r.first, r.second), n, mode, lds_level_budget);
 					ws.scratch_bytes = std::max(ws.scratch_bytes, w.scratch_bytes);
 					ws.n_counters = std::max(ws.n_counters, w.n_counters);
 				}
@@ -440,15 +452,15 @@ void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, 
 			ws.phase_hook = grid_backward_phase_hook;  // per-kernel timing when a profiler is attached
 			ws.hook_user = &timer;
 			if (level_ranges.size() <= 1) {
-				grid_backward(stream, e.grid, io, dL_denc, grid_grads, accumulate, mode, lds_level_budget, ws);
-				if (groups && groups->ready) groups->ready(groups->ctx, md.n_mlp_params(), md.n_mlp_params() + (size_t)e.grid.offset[L] * F);
+				grid_backward(stream, grid, io, dL_denc, grid_grads, accumulate, mode, lds_level_budget, ws);
+				if (groups && groups->ready) groups->ready(groups->ctx, md.n_mlp_params(), md.n_mlp_params() + (size_t)grid.offset[L] * F);
 			} else {
 				for (const auto& r : level_ranges) {
 					const uint32_t a = r.first, b = r.second;
-					const GridMeta sub = grid_levels(e.grid, a, b);
+					const GridMeta sub = grid_levels(grid, a, b);
 					timer.counts = a == 0;  // one backward pass per step, however many launches it takes
-					grid_backward(stream, sub, io, dL_denc + (size_t)a * F * stride_k, grid_grads + (size_t)e.grid.offset[a] * F, accumulate, mode, lds_level_budget, ws);
-					if (groups->ready) groups->ready(groups->ctx, md.n_mlp_params() + (size_t)e.grid.offset[a] * F, md.n_mlp_params() + (size_t)e.grid.offset[b] * F);
+					grid_backward(stream, sub, io, dL_denc + (size_t)a * F * stride_k, grid_grads + (size_t)grid.offset[a] * F, accumulate, mode, lds_level_budget, ws);
+					if (groups->ready) groups->ready(groups->ctx, md.n_mlp_params() + (size_t)grid.offset[a] * F, md.n_mlp_params() + (size_t)grid.offset[b] * F);
 				}
 			}
 		}
@@ -471,6 +483,7 @@ void encoding_forward_f32(hipStream_t stream, const Model& md, const IoLayout& l
 	if (ctx) {
 		ctx->stream = stream;
 		ctx->n = n;
+		ctx->keep_max_level(md.enc);
 	}
 	const uint32_t stride_k = 1u, stride_i = e.padded_output_width;
 	if (e.is_composite()) {
@@ -482,6 +495,7 @@ void encoding_forward_f32(hipStream_t stream, const Model& md, const IoLayout& l
 			dy_dx = ctx->dy_dx.as<float>();
 		}
 		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
+		io.max_level = e.max_level_gpu;
 		grid_forward_f32(stream, e.grid, io, params, out, dy_dx);
 		const uint32_t n_to_pad = e.padded_output_width - e.n_output_dims;
 		if (n_to_pad > 0) HIP_CHECK(hipMemset2DAsync(out + e.n_output_dims, (size_t)e.padded_output_width * sizeof(float), 0, (size_t)n_to_pad * sizeof(float), n, stream));
@@ -506,7 +520,10 @@ void encoding_backward_f32(hipStream_t stream, const Model& md, const IoLayout& 
 		}
 	} else if (e.is_grid()) {
 		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
-		if (dL_dparams && e.n_params > 0) grid_backward_f32(stream, e.grid, io, dL_doutput, dL_dparams, /*accumulate=*/false);  // GradientMode::Overwrite, cpp_api.cu:115
+		io.max_level = ctx.max_level_gpu;  // max_level as the forward pass of this context saw it
+		GridMeta grid = e.grid;
+		grid.max_level = ctx.max_level;
+		if (dL_dparams && e.n_params > 0) grid_backward_f32(stream, grid, io, dL_doutput, dL_dparams, /*accumulate=*/false);  // GradientMode::Overwrite, cpp_api.cu:115
 		if (dL_dinput) {
 			if (!ctx.dy_dx.ptr) throw std::runtime_error("backward: dL_dinput requested but forward was not run with prepare_input_gradients");
 			grid_backward_input_f32(stream, md.n_input_dims, e.n_output_dims, io, dL_doutput, ctx.dy_dx.as<float>(), dL_dinput, layout.dx_stride_i, layout.dx_stride_d);

@@ -81,6 +81,7 @@ struct Trainer {
 	bool graph_capture = false;
 	hipGraphExec_t graph_exec = nullptr;
 	uint64_t graph_warm = ~0ull;
+	uint32_t max_level_generation = 0;  // counts the changes of the grid's max_level / max_level_gpu: part of a step's shape, so the step after one runs plainly
 	uint32_t graph_signature = 0;  // OptimizerChain::next_step_signature() of the step `graph_exec` was instantiated from
 	uint64_t graph_launches = 0, graph_instantiations = 0;
 	// data-parallel hosts: called between backward and the optimizer (tcnn_trainer_set_gradient_exchange)

@@ -125,6 +125,9 @@ _sig("tcnn_module_set_jit_fusion", _i, _vp, _i)
 _sig("tcnn_module_grid_indices", _i, _vp, _vp, _u32, _vp, _vp)
 _sig("tcnn_module_grid_level_n_params", _i, _vp, _u32, C.POINTER(_sz))
 _sig("tcnn_module_grid_level_params_offset", _i, _vp, _u32, C.POINTER(_sz))
+_sig("tcnn_module_set_max_level", _i, _vp, _f)
+_sig("tcnn_module_max_level", _i, _vp, C.POINTER(_f))
+_sig("tcnn_module_set_max_level_gpu", _i, _vp, _vp)
 _sig("tcnn_module_n_nested", _u32, _vp)
 _sig("tcnn_module_nested_layout", _i, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz))
 _sig("tcnn_create_from_config", _i, _u32, _u32, _cp, _u32, C.POINTER(_vp))
@@ -179,6 +182,9 @@ _sig("tcnn_trainer_get_stage_times", _i, _vp, _vp, _vp)
 _sig("tcnn_trainer_set_lds_level_budget", _i, _vp, _u32)
 _sig("tcnn_trainer_set_graph_capture", _i, _vp, _i)
 _sig("tcnn_trainer_graph_capture_stats", _i, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+_sig("tcnn_trainer_set_max_level", _i, _vp, _f)
+_sig("tcnn_trainer_max_level", _i, _vp, C.POINTER(_f))
+_sig("tcnn_trainer_set_max_level_gpu", _i, _vp, _vp)
 _sig("tcnn_get_fused_network_passes", _i)
 _sig("tcnn_set_fused_network_passes", _i, _i)
 _sig("tcnn_set_finalize_in_optimizer", _i, _i)
@@ -547,6 +553,22 @@ class Module:
         _check(_lib.tcnn_module_grid_level_params_offset(self._h, level, C.byref(v)))
         return v.value
 
+    # MultiLevelEncoding::max_level / set_max_level / set_max_level_gpu (multi_level_interface.h:101-123): a lone grid's run-time state
+    def max_level(self):
+        v = C.c_float()
+        _check(_lib.tcnn_module_max_level(self._h, C.byref(v)))
+        return float(v.value)
+
+    def set_max_level(self, value):
+        _check(_lib.tcnn_module_set_max_level(self._h, float(value)))
+
+    def set_max_level_gpu(self, values):
+        """values: a contiguous one-dimensional float32 GPU tensor with one entry per row of every later input, or None.  The library keeps
+        the POINTER only: the caller keeps the tensor alive (modules.py does)."""
+        if values is not None and (not values.is_cuda or not values.is_contiguous() or values.dtype != torch.float32 or values.dim() != 1):
+            raise RuntimeError("set_max_level_gpu: expected a contiguous one-dimensional float32 GPU tensor")
+        _check(_lib.tcnn_module_set_max_level_gpu(self._h, _ptr(values)))
+
     def nested_layout(self):
         """The nested encodings of a Composite, in order (empty for every other module): where each reads its input dims, writes its rows of the
         (unreduced) encoded matrix and keeps its parameters."""
@@ -592,7 +614,7 @@ class ExtModule:
     def __init__(self, m):
         self._m = m
         self._h = C.c_void_p(m.handle())
-        for name in ("fwd", "bwd", "bwd_bwd_input", "initial_params", "n_input_dims", "n_params", "n_output_dims", "name"):
+        for name in ("fwd", "bwd", "bwd_bwd_input", "initial_params", "n_input_dims", "n_params", "n_output_dims", "name", "max_level", "set_max_level", "set_max_level_gpu"):
             setattr(self, name, getattr(m, name))
         self._param_precision = Precision(m.param_precision())
         self._output_precision = Precision(m.output_precision())

@@ -42,6 +42,9 @@ struct Abi {  // include/tcnn_hip.h, the entries this binding calls
 	const char* (*name)(const tcnn_module*) = nullptr;
 	int (*jit_fusion)(const tcnn_module*) = nullptr;
 	int (*set_jit_fusion)(tcnn_module*, int) = nullptr;
+	int (*set_max_level)(tcnn_module*, float) = nullptr;
+	int (*max_level)(const tcnn_module*, float*) = nullptr;
+	int (*set_max_level_gpu)(tcnn_module*, const float*) = nullptr;
 	uint32_t (*batch_size_granularity)() = nullptr;
 	float (*default_loss_scale)(int) = nullptr;
 	bool bound = false;
@@ -79,6 +82,9 @@ void bind_library(const std::string& path) {
 	resolve(lib, capi.name, "tcnn_module_name");
 	resolve(lib, capi.jit_fusion, "tcnn_module_jit_fusion");
 	resolve(lib, capi.set_jit_fusion, "tcnn_module_set_jit_fusion");
+	resolve(lib, capi.set_max_level, "tcnn_module_set_max_level");
+	resolve(lib, capi.max_level, "tcnn_module_max_level");
+	resolve(lib, capi.set_max_level_gpu, "tcnn_module_set_max_level_gpu");
 	resolve(lib, capi.batch_size_granularity, "tcnn_batch_size_granularity");
 	resolve(lib, capi.default_loss_scale, "tcnn_default_loss_scale");
 	capi.bound = true;
@@ -229,6 +235,24 @@ public:
 	std::string name() const { return capi.name(m_); }
 	bool jit_fusion() const { return capi.jit_fusion(m_) != 0; }
 	void set_jit_fusion(bool val) { check(capi.set_jit_fusion(m_, val ? 1 : 0)); }
+	// MultiLevelEncoding::max_level / set_max_level / set_max_level_gpu (a lone grid; the library refuses every other module)
+	float max_level() const {
+		float v = 0.0f;
+		check(capi.max_level(m_, &v));
+		return v;
+	}
+	void set_max_level(float value) { check(capi.set_max_level(m_, value)); }
+	// fp32 CUDA tensor with one entry per row of every later input, or None; the CALLER keeps it alive (modules.py does)
+	void set_max_level_gpu(const c10::optional<torch::Tensor>& values) {
+		if (!values.has_value()) {
+			check(capi.set_max_level_gpu(m_, nullptr));
+			return;
+		}
+		if (!values->is_cuda() || !values->is_contiguous() || values->scalar_type() != torch::kFloat32 || values->dim() != 1) {
+			throw std::runtime_error("set_max_level_gpu: expected a contiguous one-dimensional float32 GPU tensor");
+		}
+		check(capi.set_max_level_gpu(m_, values->data_ptr<float>()));
+	}
 	uintptr_t handle() const { return (uintptr_t)m_; }  // for the ctypes helpers of _C.py (grid_indices, level tables)
 
 private:
@@ -359,6 +383,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 		.def("hyperparams_json", &Module::hyperparams_json)
 		.def("name", &Module::name)
 		.def("handle", &Module::handle)
+		.def("max_level", &Module::max_level)
+		.def("set_max_level", &Module::set_max_level)
+		.def("set_max_level_gpu", &Module::set_max_level_gpu)
 		.def_property("jit_fusion", &Module::jit_fusion, &Module::set_jit_fusion);
 	m.def("create_network_with_input_encoding", &create_network_with_input_encoding);
 	m.def("create_network", &create_network);

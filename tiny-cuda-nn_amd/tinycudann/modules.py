@@ -119,9 +119,23 @@ def _precision_dtype(native_module):
     return _torch_precision(native_module.output_precision())
 
 
+class _KeepAlive(torch.autograd.Function):
+    """y, unchanged, with `keep` held for as long as the graph through y lives: the per-sample max_level array a pending backward will read."""
+
+    @staticmethod
+    def forward(ctx, y, keep):
+        ctx.keep = keep
+        return y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy, None
+
+
 class Module(torch.nn.Module):
     def __init__(self, seed=1337):
         super().__init__()
+        self._max_level_gpu = None
         self.native_tcnn_module = self._native_tcnn_module()
         self.dtype = _torch_precision(self.native_tcnn_module.param_precision())
         self.seed = seed
@@ -139,16 +153,29 @@ class Module(torch.nn.Module):
             x = torch.nn.functional.pad(x, [0, 0, 0, padded - batch_size])
         if x.dtype != torch.float32 or not x.is_contiguous():
             x = x.to(torch.float).contiguous()
+        max_level_gpu = self._max_level_gpu
+        if max_level_gpu is not None:
+            # one entry per row of the PADDED batch is read: rows the padding added get 1.0 (their output is sliced away below)
+            if max_level_gpu.shape[0] < batch_size:
+                raise RuntimeError(f"max_level_gpu holds {max_level_gpu.shape[0]} entries, the input has {batch_size} rows")
+            if max_level_gpu.device != x.device:
+                raise RuntimeError("max_level_gpu must live on the input's device")
+            if max_level_gpu.shape[0] < padded:
+                max_level_gpu = torch.nn.functional.pad(max_level_gpu, [0, padded - max_level_gpu.shape[0]], value=1.0)
+            self.native_tcnn_module.set_max_level_gpu(max_level_gpu)
         if _C.EXT is not None:  # the compiled binding: one C++ autograd node (ext/torch_module.cpp NativeFunction)
             y = _C.ext_apply(self.native_tcnn_module, x, self.params.to(self.dtype).contiguous(), self.loss_scale)
         else:
             y = _NativeFunction.apply(self.native_tcnn_module, x, self.params.to(self.dtype).contiguous(), self.loss_scale)
+        if max_level_gpu is not None and y.requires_grad:
+            y = _KeepAlive.apply(y, max_level_gpu)  # the backward passes of this call read the array this call read
         # (one slicing node in the graph where the batch needed no padding: the common case at training batch sizes)
         return y[:, : self.n_output_dims] if padded == batch_size else y[:batch_size, : self.n_output_dims]
 
     def __getstate__(self):
         state = self.__dict__.copy()
         del state["native_tcnn_module"]  # native handles are rebuilt, not pickled
+        state["_max_level_gpu"] = None  # run-time state of the native object, gone with it (the scalar is back at 1.0 too)
         return state
 
     def __setstate__(self, state):
@@ -158,6 +185,28 @@ class Module(torch.nn.Module):
     def extra_repr(self):
         return (f"n_input_dims={self.n_input_dims}, n_output_dims={self.n_output_dims}, seed={self.seed}, "
                 f"dtype={self.dtype}, hyperparams={self.native_tcnn_module.hyperparams()}")
+
+    # MultiLevelEncoding::max_level / set_max_level / set_max_level_gpu (multi_level_interface.h:101-123): modules whose encoding is a single
+    # grid; the library raises for every other one.  Run-time state: not a hyperparameter, not in the state dict, not pickled.
+    @property
+    def max_level(self):
+        return self.native_tcnn_module.max_level()
+
+    @max_level.setter
+    def max_level(self, value):
+        self.native_tcnn_module.set_max_level(float(value))
+
+    def set_max_level_gpu(self, values):
+        """One max_level per row of x (float32, on the module's device, at least as many entries as x has rows), which then wins over the
+        scalar; None clears it.  The module keeps a reference, and every graph built while it is set keeps one until it is freed."""
+        if values is not None:
+            if not torch.is_tensor(values) or values.dtype != torch.float32 or values.dim() != 1 or not values.is_cuda:
+                raise RuntimeError("set_max_level_gpu: expected a one-dimensional float32 GPU tensor (or None)")
+            if values.device != self.params.device:
+                raise RuntimeError("set_max_level_gpu: the tensor must live on the module's device")
+            values = values.detach().contiguous()
+        self.native_tcnn_module.set_max_level_gpu(values)  # (raises for a module without a lone grid, before anything is kept)
+        self._max_level_gpu = values
 
     @property
     def jit_fusion(self):

@@ -155,14 +155,19 @@ class TrainableModel:
         _check(_lib.tcnn_trainer_training_step(self._h, _stream(), input.shape[0], _ptr(input), _ptr(target), _ptr(data_pdf),
                                                int(run_optimizer), _ptr(dL_dinput), int(use_inference_params), int(gradient_mode),
                                                _ptr(external_dL_dy), C.byref(h) if want_context else None))
-        return ForwardContext(h, input.shape[0], self.padded_output_width, self) if want_context else None
+        return self._context(h, input.shape[0]) if want_context else None
 
     def forward(self, input, target, loss_scale=128.0, data_pdf=None, prepare_input_gradients=False, external_dL_dy=None):
         self._check_io(input, target)
         h = C.c_void_p()
         _check(_lib.tcnn_trainer_forward(self._h, _stream(), loss_scale, input.shape[0], _ptr(input), _ptr(target), _ptr(data_pdf), 0,
                                          int(prepare_input_gradients), _ptr(external_dL_dy), C.byref(h)))
-        return ForwardContext(h, input.shape[0], self.padded_output_width, self)
+        return self._context(h, input.shape[0])
+
+    def _context(self, h, n):
+        ctx = ForwardContext(h, n, self.padded_output_width, self)
+        ctx._max_level_gpu = getattr(self, "_max_level_gpu", None)  # a later backward(ctx) reads the array this pass read: alive as long as ctx
+        return ctx
 
     def backward(self, ctx, input, dL_dinput=None, gradient_mode=GradientMode.Overwrite):
         _check(_lib.tcnn_trainer_backward(self._h, _stream(), ctx._h, input.shape[0], _ptr(input), _ptr(dL_dinput), 0, int(gradient_mode)))
@@ -360,6 +365,26 @@ class TrainableModel:
     def set_graph_capture(self, enable=True):
         """training_step as one graph launch on non-null streams (trainer.h:343-350: the reference captures its passes into a CUDA graph)."""
         _check(_lib.tcnn_trainer_set_graph_capture(self._h, int(enable)))
+
+    # MultiLevelEncoding::max_level / set_max_level / set_max_level_gpu of the model's grid encoding (tcnn_trainer_set_max_level): run-time
+    # state, in force from the next training_step / forward / inference on
+    @property
+    def max_level(self):
+        v = C.c_float()
+        _check(_lib.tcnn_trainer_max_level(self._h, C.byref(v)))
+        return float(v.value)
+
+    @max_level.setter
+    def max_level(self, value):
+        _check(_lib.tcnn_trainer_set_max_level(self._h, float(value)))
+
+    def set_max_level_gpu(self, values):
+        """One max_level per sample of every later batch (contiguous one-dimensional float32 GPU tensor), which then wins over the scalar;
+        None clears it.  The model keeps a reference to the tensor, and so does every context made while it is set."""
+        if values is not None and (not values.is_cuda or not values.is_contiguous() or values.dtype != torch.float32 or values.dim() != 1):
+            raise RuntimeError("set_max_level_gpu: expected a contiguous one-dimensional float32 GPU tensor")
+        _check(_lib.tcnn_trainer_set_max_level_gpu(self._h, _ptr(values)))
+        self._max_level_gpu = values
 
     def graph_capture_stats(self):
         """(graph launches, graph instantiations) so far."""
