@@ -14,7 +14,7 @@
 #if defined(TCNN_EXPERIMENT)
 extern "C" __attribute__((weak, visibility("default"))) int tcnn_experiment_build_marker = 1;
 #else
-#if defined(TCNN_EXP_DIAG_SCATTER) || defined(TCNN_EXP_DIAG_OWNER)
+#if defined(TCNN_EXP_DIAG_SCATTER) || defined(TCNN_EXP_DIAG_OWNER) || defined(TCNN_EXP_COUNT_ZERO_PAIRS)
 #error "TCNN_EXP_* switches exist in experiment builds only: add -DTCNN_EXPERIMENT (scripts/build_variant_one.sh does)"
 #endif
 #endif
@@ -31,5 +31,31 @@ constexpr uint32_t EXP_DIAG_SCATTER = 0u;
 constexpr uint32_t EXP_DIAG_OWNER = TCNN_EXP_DIAG_OWNER;
 #else
 constexpr uint32_t EXP_DIAG_OWNER = 0u;
+#endif
+// k_grid_bucket_scatter with -DTCNN_EXP_COUNT_ZERO_PAIRS: counts, per level, the pair records it derives and those whose payloads are all
+// +-0 (global atomics per pair: the kernel's TIME means nothing in such a build, its results are the shipped ones);
+// tcnn_exp_zero_pair_counts() reads the table (scripts/exp_zero_records.py).  The table and its reader are defined HERE: the switch goes
+// to the ONE object that holds the scatter (scripts/build_variant_one.sh ... grid_backward_scatter), which includes this header after
+// grid_backward_plan.h.
+#if defined(TCNN_EXP_COUNT_ZERO_PAIRS)
+constexpr bool EXP_COUNT_ZERO_PAIRS = true;
+__device__ unsigned long long g_exp_pair_counts[MAX_N_LEVELS][2];
+TCNN_DEVICE void exp_count_pair(uint32_t level, bool zero) {
+	atomicAdd(&g_exp_pair_counts[level][0], 1ull);
+	if (zero) atomicAdd(&g_exp_pair_counts[level][1], 1ull);
+}
+// out: [MAX_N_LEVELS][2] = {pairs, all-zero pairs} since the last reset (may be null); returns MAX_N_LEVELS, or -1
+extern "C" __attribute__((visibility("default"), used)) int tcnn_exp_zero_pair_counts(unsigned long long* out, int reset) {
+	if (hipDeviceSynchronize() != hipSuccess) return -1;
+	if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_exp_pair_counts), sizeof(g_exp_pair_counts)) != hipSuccess) return -1;
+	if (reset) {
+		static const unsigned long long zeros[MAX_N_LEVELS][2] = {};
+		if (hipMemcpyToSymbol(HIP_SYMBOL(g_exp_pair_counts), zeros, sizeof(zeros)) != hipSuccess) return -1;
+	}
+	return (int)MAX_N_LEVELS;
+}
+#else
+constexpr bool EXP_COUNT_ZERO_PAIRS = false;
+constexpr void exp_count_pair(uint32_t, bool) {}  // (constexpr: callable from host and device code alike)
 #endif
 }  // namespace tcnn_hip

@@ -355,7 +355,7 @@ static void grid_backward_sliced_launches(hipStream_t stream, const GridMeta& me
 	if (bk.n_levels) {
 		if (ws.phase_hook) ws.phase_hook(ws.hook_user, 0, 1);
 		// pass A: derive every corner once, bin by owner (+ zero the gradients of chunked levels)
-		launch_bucket_scatter(stream, meta, io, bk, dL_dy, counters, queues, overflow, grid_gradient);
+		launch_bucket_scatter(stream, meta, io, bk, dL_dy, counters, queues, overflow, grid_gradient, accumulate);
 		if (ws.phase_hook) ws.phase_hook(ws.hook_user, 0, 0);
 	}
 	if (ws.phase_hook) ws.phase_hook(ws.hook_user, 1, 1);

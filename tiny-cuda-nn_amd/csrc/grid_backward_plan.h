@@ -292,7 +292,7 @@ inline BackwardPlan make_backward_plan(const GridMeta& meta, uint32_t n, bool pa
 // The two passes of the bucketed mode, each launched from the file that holds its kernel (grid_backward_scatter.hip, grid_backward_owner.hip);
 // grid_backward.hip runs them in turn.  `counters`, `queues`, `overflow`: the three parts of the GridBackwardWorkspace.
 void launch_bucket_scatter(hipStream_t stream, const GridMeta& meta, const GridIO& io, const BucketPlan& plan, const half_t* dL_dy, uint32_t* counters,
-                           uint32_t* queues, uint32_t* overflow, half_t* grid_gradient);
+                           uint32_t* queues, uint32_t* overflow, half_t* grid_gradient, bool accumulate);
 // pass B of the plan's bucket items in the packed kernel; force_wide: every slice through its 64-bit redo (grid_owner_mode() == 2)
 void launch_bucket_owners(hipStream_t stream, const GridMeta& meta, const BackwardPlan& bp, bool accumulate, bool force_wide, uint32_t* counters,
                           const uint32_t* queues, const uint32_t* overflow, half_t* grid_gradient);

@@ -28,12 +28,13 @@ template <uint32_t D, uint32_t F, bool SECOND_ORDER>
 __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const GridMeta meta, const GridIO io, const BucketPlan plan,
                                                                          const half_t* __restrict__ dL_dy, uint32_t* __restrict__ counters,
                                                                          uint32_t* __restrict__ queues, uint32_t* __restrict__ overflow,
-                                                                         half_t* __restrict__ grid_gradient) {
+                                                                         half_t* __restrict__ grid_gradient, const int accumulate) {
 	constexpr uint32_t N_CORNERS = 1u << D, PW = BucketRecord<F>::PAYLOAD_WORDS, W = BucketRecord<F>::WORDS, PWP = BucketRecord<F>::PAIR_WORDS;
 	constexpr uint32_t N_PAIRS_PER_SAMPLE = N_CORNERS / 2;
 	constexpr uint32_t SPT = bucket_spt(D, F), TILE = SPT * BUCKET_THREADS, N_PAIR = TILE * N_PAIRS_PER_SAMPLE;
 	TCNN_DYN_LDS(lds_raw);
 	constexpr uint32_t diag_scatter = EXP_DIAG_SCATTER;  // 0 in the product build (exp_diag.h)
+	constexpr uint32_t PAYLOAD_MAGNITUDE = F == 1 ? 0x7FFFFFFFu : 0x7FFF7FFFu;  // a payload word without its sign bit(s): one fp32, or two 16-bit values
 	if (blockIdx.x >= plan.scatter_blocks) {
 		// gradients of chunked levels are accumulated with atomics by several owners in pass B: zero them here
 		const uint32_t z = blockIdx.x - plan.scatter_blocks;
@@ -51,6 +52,20 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 	const bool per_sample = io.max_level != nullptr;
 	if (!per_sample && level_is_off<false>(meta, level, F)) return;  // no records, the owners store zeros
 	const Level<D> lv = make_level<D>(meta, level);
+	// Zero records.  Under the loss scale the products (GRAD_T)weight * dL/dy underflow to +-0 in 16 bits for much of a converged fit.  The owners
+	// sum in exact fixed point and store +0 for an entry nothing was added to, so a record of zeros changes no bit of the gradient: a pair whose
+	// two payloads are all +-0 is not ranked, staged or queued, and a zero record that would travel through the overflow list is not pushed.
+	// The one place that could tell: a chunked level in GradientMode::Accumulate.  Its slices are neither cleared nor stored, only added to where
+	// an owner's sum is non-zero, so an entry may still hold the caller's -0 when the last owner drains a long overflow list with global
+	// atomics, and -0 + +0 is +0.  Such a level keeps every record (everywhere else the slice has been stored by then and holds no -0).
+#if defined(TCNN_TEST_KEEP_ZERO_RECORDS)  // tests/emu: the kernel as it was before zero records were dropped, for the bit-for-bit comparison
+#if !defined(TCNN_HOST_EMU)
+#error "TCNN_TEST_KEEP_ZERO_RECORDS is a switch of the host emulator's test builds (tests/emu/emu_zero_records.py)"
+#endif
+	const bool keep_zero = true;
+#else
+	const bool keep_zero = accumulate != 0 && plan.n_chunks[j] > 1u;
+#endif
 
 	// Queue unit: a PAIR of records -- the two corners that differ in dimension 0 only.  Their table entries are
 	// neighbours (dense index +1; hashed: prime[0] == 1, so the indices differ in the low bits only) and therefore
@@ -179,7 +194,18 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 				}
 #pragma unroll
 				for (uint32_t pr = 0; pr < N_PAIRS_PER_SAMPLE; ++pr) {
-					const bool live = valid && (pr == 0u || !lv.nearest);
+					// a record whose payload is +-0 in every word adds nothing to the owners' exact sums: it is not created (see keep_zero above)
+					uint32_t mag0 = 0u, mag1 = 0u;
+#pragma unroll
+					for (uint32_t p = 0; p < PW; ++p) {
+						mag0 |= pay[s][2 * pr][p];
+						mag1 |= pay[s][2 * pr + 1][p];
+					}
+					const bool nz0 = keep_zero || (mag0 & PAYLOAD_MAGNITUDE) != 0u, nz1 = keep_zero || (mag1 & PAYLOAD_MAGNITUDE) != 0u;
+					if constexpr (EXP_COUNT_ZERO_PAIRS) {  // (false in the product build, exp_diag.h: the pairs of the level, and the all-zero ones among them)
+						if (valid && (pr == 0u || !lv.nearest)) exp_count_pair(level, ((mag0 | (lv.nearest ? 0u : mag1)) & PAYLOAD_MAGNITUDE) == 0u);
+					}
+					const bool live = valid && (pr == 0u || !lv.nearest) && (nz0 || (nz1 && !lv.nearest));
 					const uint32_t bucket = ridx[s][2 * pr] >> shift;
 					if (!live) {
 						ridx[s][2 * pr] = BUCKET_INVALID_INDEX;
@@ -188,7 +214,7 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 						ridx[s][2 * pr + 1] = BUCKET_INVALID_INDEX;
 					} else if constexpr (FAST) {
 						if (!fast_together) {
-							push_overflow(ridx[s][2 * pr + 1], pay[s][2 * pr + 1]);
+							if (nz1) push_overflow(ridx[s][2 * pr + 1], pay[s][2 * pr + 1]);
 							ridx[s][2 * pr + 1] = BUCKET_INVALID_INDEX;
 						}
 						ridx[s][2 * pr] |= fast_tag;
@@ -198,7 +224,7 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 						const uint32_t word0 = ridx[s][2 * pr] | PAIR_HAS_SECOND;
 						const uint32_t i1 = ridx[s][2 * pr + 1];
 						if ((i1 >> shift) != bucket || pair_second_index<D>(lv, word0) != i1) {
-							push_overflow(i1, pay[s][2 * pr + 1]);
+							if (nz1) push_overflow(i1, pay[s][2 * pr + 1]);
 							ridx[s][2 * pr + 1] = BUCKET_INVALID_INDEX;
 						} else {
 							ridx[s][2 * pr] = word0;
@@ -305,8 +331,15 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 #pragma unroll
 				for (uint32_t w = 0; w < PWP; ++w) queue_store(dst + w, rec[w]);
 			} else {
-				push_overflow(rec[0] & PAIR_INDEX_MASK, &rec[1]);
-				if (rec[0] & PAIR_HAS_SECOND) push_overflow(pair_second_index<D>(lv, rec[0]), &rec[1 + PW]);
+				// (a pair is queued when either record is non-zero: the zero half of a spilled pair stays out of the list like any zero record)
+				uint32_t mag0 = 0u, mag1 = 0u;
+#pragma unroll
+				for (uint32_t p = 0; p < PW; ++p) {
+					mag0 |= rec[1 + p];
+					mag1 |= rec[1 + PW + p];
+				}
+				if (keep_zero || (mag0 & PAYLOAD_MAGNITUDE)) push_overflow(rec[0] & PAIR_INDEX_MASK, &rec[1]);
+				if ((rec[0] & PAIR_HAS_SECOND) && (keep_zero || (mag1 & PAYLOAD_MAGNITUDE))) push_overflow(pair_second_index<D>(lv, rec[0]), &rec[1 + PW]);
 			}
 		}
 		__syncthreads();  // the staging area and the offsets are reused by the next tile
@@ -333,7 +366,7 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 }
 
 void launch_bucket_scatter(hipStream_t stream, const GridMeta& meta, const GridIO& io, const BucketPlan& plan, const half_t* dL_dy, uint32_t* counters,
-                           uint32_t* queues, uint32_t* overflow, half_t* grid_gradient) {
+                           uint32_t* queues, uint32_t* overflow, half_t* grid_gradient, bool accumulate) {
 	// the scatter's workgroups, then the blocks that zero the gradients of chunked levels
 	const uint32_t blocks = plan.scatter_blocks + plan.zero_block_begin[plan.n_levels];
 	uint32_t max_buckets = 0;
@@ -343,11 +376,11 @@ void launch_bucket_scatter(hipStream_t stream, const GridMeta& meta, const GridI
 		if (io.ddx) {
 			TCNN_SET_MAX_DYN_LDS((k_grid_bucket_scatter<D, F, true>), lds);
 			TCNN_LAUNCH((k_grid_bucket_scatter<D, F, true>), dim3(blocks), dim3(BUCKET_THREADS), lds, stream, meta, io, plan, dL_dy, counters, queues, overflow,
-			            grid_gradient);
+			            grid_gradient, accumulate ? 1 : 0);
 		} else {
 			TCNN_SET_MAX_DYN_LDS((k_grid_bucket_scatter<D, F, false>), lds);
 			TCNN_LAUNCH((k_grid_bucket_scatter<D, F, false>), dim3(blocks), dim3(BUCKET_THREADS), lds, stream, meta, io, plan, dL_dy, counters, queues, overflow,
-			            grid_gradient);
+			            grid_gradient, accumulate ? 1 : 0);
 		}
 	});
 }
