@@ -1,6 +1,8 @@
 // mlp_general.hip -- the layer-by-layer network for what the fused kernels are not built for (mlp_kernels.h mlp_layer_by_layer): hidden
 // widths that are a multiple of 16 up to MLP_GENERAL_MAX_WIDTH other than 16 / 32 / 64 / 128, and -- at every width -- the hidden
-// activations whose derivative needs the pre-activation (SiLU, Sine).  Stands where the reference's CutlassMLP stands (cutlass_mlp.cu:110-330: one GEMM
+// activations whose derivative needs the pre-activation (SiLU, Sine) and more than MLP_MAX_OUT_WIDTH padded outputs (up to
+// MLP_GENERAL_MAX_OUT_WIDTH: the output matrix is one more M x K product, the weight-gradient tiles cover any row count).
+// Stands where the reference's CutlassMLP stands (cutlass_mlp.cu:110-330: one GEMM
 // with an activation epilogue per layer, one GEMM per layer for dL/d(pre-activation), one split-K GEMM per weight matrix) -- its BEHAVIOUR,
 // not its tiling.  Same parameter layout, transposed scratch and boundary layouts as the fused kernels (mlp_kernels.h), so everything
 // above the launchers is shared.
@@ -12,7 +14,9 @@
 //     the accumulator to 16 bits, stores it into the stack's second block (training) and applies the activation to the rounded value;
 //     backward multiplies the rounded accumulator by the rounded derivative at that saved pre-activation.  Both operands have k contiguous, so the
 //     weights are the MFMA A operand and the activations the B operand straight out of [row][k] LDS tiles, and the accumulator fragment
-//     (4 consecutive m for one sample) is an 8-byte store into the sample-major result.
+//     (4 consecutive m for one sample) is an 8-byte store into the sample-major result.  The output layer of an inference into the caller's
+//     fp32 matrix (GEN_EPI_FORWARD_F32, MlpF32Output) rounds to 16 bits like that store, widens the rounded values and stores the columns
+//     below the unpadded width with the caller's strides: the bits of the padded 16-bit matrix put through trim_and_cast, without the matrix.
 //     Workgroup: 4 waves, tile = (16 * NMB m) x (128 samples); wave w owns samples 32w .. 32w+31 and all NMB blocks of m
 //     (2 B reads + NMB A reads per 2 * NMB MFMAs).  K runs in steps of 64 through two LDS stages: the global loads of step s + 1 are
 //     issued into registers before the MFMAs of step s and written to the other stage after them -- one barrier per step.
@@ -45,7 +49,8 @@ constexpr uint32_t GEN_LDK = GEN_BK + 8;   // row stride (halves) of the [row][k
 constexpr uint32_t GEN_MAX_MB = 4;         // blocks of 16 m per workgroup tile, at most
 
 // _PRE: the epilogues of the activations that keep their pre-activation (SiLU / Sine, activation_device.h act_forward4_pre / act_backward4_pre)
-enum : uint32_t { GEN_EPI_NONE = 0, GEN_EPI_FORWARD = 1, GEN_EPI_BACKWARD = 2, GEN_EPI_FORWARD_PRE = 3, GEN_EPI_BACKWARD_PRE = 4 };
+// _F32: GEN_EPI_FORWARD whose result goes to the caller's fp32 matrix (Yf ...) instead of Y
+enum : uint32_t { GEN_EPI_NONE = 0, GEN_EPI_FORWARD = 1, GEN_EPI_BACKWARD = 2, GEN_EPI_FORWARD_PRE = 3, GEN_EPI_BACKWARD_PRE = 4, GEN_EPI_FORWARD_F32 = 5 };
 
 struct GenLayerArgs {
 	uint32_t n, M, K;
@@ -58,7 +63,35 @@ struct GenLayerArgs {
 	uint32_t ldf;         // GEN_EPI_BACKWARD_PRE: the PRE-activation values, same layout
 	uint32_t act;
 	half_t* P;            // GEN_EPI_FORWARD_PRE: where the rounded pre-activations go, sample-major [n][ldy]; null: not saved (inference)
+	// GEN_EPI_FORWARD_F32: element (sample i, m) with m < f_dims at Yf[i * f_stride_i + m * f_stride_j].  f_vec: floats per store the host
+	// proved aligned for EVERY (sample, m = multiple of 4) -- 4 or 2 only with f_stride_j == 1 (gen_f32_vec) -- else 1
+	float* Yf;
+	uint32_t f_dims, f_stride_i, f_stride_j, f_vec;
 };
+
+// the 4 values of one accumulator fragment (m .. m + 3 of one sample), widened, into the caller's fp32 matrix: one 16-byte store where the host
+// proved that alignment and all 4 columns exist; else 8-byte stores per existing pair where it proved that, a lone last column on its own;
+// else column by column.  Nothing at or past f_dims is written.
+TCNN_DEVICE void gen_store_f32(const GenLayerArgs& a, size_t sample, uint32_t m, h4 o) {
+	const f4 v = f4{(float)o[0], (float)o[1], (float)o[2], (float)o[3]};
+	float* p = a.Yf + sample * a.f_stride_i + (size_t)m * a.f_stride_j;
+	if (a.f_vec == 4u && m + 4u <= a.f_dims) {
+		*(f4*)p = v;
+	} else if (a.f_vec >= 2u) {
+#pragma unroll
+		for (uint32_t q = 0; q < 2; ++q) {
+			if (m + 2u * q + 2u <= a.f_dims) {
+				*(f2*)(p + 2u * q) = f2{v[2 * q], v[2 * q + 1]};
+			} else if (m + 2u * q < a.f_dims) {
+				p[2u * q] = v[2 * q];
+			}
+		}
+	} else {
+#pragma unroll
+		for (uint32_t r = 0; r < 4; ++r)
+			if (m + r < a.f_dims) p[(size_t)r * a.f_stride_j] = v[r];
+	}
+}
 
 template <uint32_t NMB, uint32_t EPI, bool X_FM, bool Y_FM, bool GENERAL>
 __global__ void __launch_bounds__(GEN_THREADS) k_mlp_general_layer(const GenLayerArgs a) {
@@ -171,7 +204,7 @@ __global__ void __launch_bounds__(GEN_THREADS) k_mlp_general_layer(const GenLaye
 		for (uint32_t sb = 0; sb < 2; ++sb) {
 			const size_t sample = s0 + 32 * w + 16 * sb + lr;
 			h4 o;
-			if constexpr (EPI == GEN_EPI_FORWARD) {
+			if constexpr (EPI == GEN_EPI_FORWARD || EPI == GEN_EPI_FORWARD_F32) {
 				o = act_forward4<GENERAL>(a.act, acc[mb][sb]);
 			} else if constexpr (EPI == GEN_EPI_BACKWARD) {
 				const h4 fv = *(const h4*)(a.F + sample * a.ldf + m);
@@ -190,7 +223,9 @@ __global__ void __launch_bounds__(GEN_THREADS) k_mlp_general_layer(const GenLaye
 				o = h4{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
 			}
 			if (valid) {
-				if constexpr (Y_FM) {
+				if constexpr (EPI == GEN_EPI_FORWARD_F32) {
+					gen_store_f32(a, sample, m, o);
+				} else if constexpr (Y_FM) {
 #pragma unroll
 					for (uint32_t r = 0; r < 4; ++r) a.Y[(size_t)(m + r) * a.n + sample] = o[r];
 				} else {
@@ -368,8 +403,21 @@ static void gen_launch_layer(hipStream_t stream, const GenLayerArgs& a) {
 #undef TCNN_GEN_LAUNCH
 }
 
-void mlp_general_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, half_t* hidden, half_t* output) {
+// floats per store of gen_store_f32: rows start stride_i floats apart and a fragment at a multiple of 4 columns, so with unit column
+// stride a 16-byte (8-byte) store is aligned everywhere iff the base is and stride_i is a multiple of 4 (2)
+static uint32_t gen_f32_vec(const MlpF32Output& f) {
+	if (f.stride_j != 1u) return 1u;
+	const uintptr_t base = (uintptr_t)f.out;
+	if (base % 16u == 0u && f.stride_i % 4u == 0u) return 4u;
+	if (base % 8u == 0u && f.stride_i % 2u == 0u) return 2u;
+	return 1u;
+}
+
+void mlp_general_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, half_t* hidden, half_t* output,
+                         const MlpF32Output& f32) {
 	const uint32_t W = m.width, HM = m.n_hidden_matmuls;
+	if (f32.out && (hidden || output)) throw std::runtime_error("mlp_general_forward: the fp32 output is for inference, in place of the 16-bit one");
+	if (f32.out && (f32.dims == 0 || f32.dims > m.padded_out)) throw std::runtime_error("mlp_general_forward: the fp32 output has at most padded_out columns");
 	// inference keeps two ping-pong activation matrices [n][W] instead of the saved stack: stream-ordered scratch of this call
 	const size_t layer_elems = (size_t)n * W;
 	half_t* ping = nullptr;
@@ -410,8 +458,17 @@ void mlp_general_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const
 		x = y;
 		K = W;
 	}
-	const GenLayerArgs a = {n, m.padded_out, W, Wl, x, W, output, m.padded_out, nullptr, 0u, m.output_activation, nullptr};
-	gen_launch_layer<GEN_EPI_FORWARD, false, false>(stream, a);
+	GenLayerArgs a = {n, m.padded_out, W, Wl, x, W, output, m.padded_out, nullptr, 0u, m.output_activation, nullptr};
+	if (f32.out) {
+		a.Yf = f32.out;
+		a.f_dims = f32.dims;
+		a.f_stride_i = f32.stride_i;
+		a.f_stride_j = f32.stride_j;
+		a.f_vec = gen_f32_vec(f32);
+		gen_launch_layer<GEN_EPI_FORWARD_F32, false, false>(stream, a);
+	} else {
+		gen_launch_layer<GEN_EPI_FORWARD, false, false>(stream, a);
+	}
 }
 
 // The fp32 slabs of all slices may take this much scratch.  512 slabs (what the fused kernels write) of a 1024 x 4 network would be 8 GB.

@@ -2,7 +2,8 @@
 // layer-by-layer network (mlp_general.hip, the reference's CutlassMLP) for every other multiple of 16 up to MLP_GENERAL_MAX_WIDTH.
 // Both sit behind the same launchers (mlp_forward / mlp_backward / ...) with the same parameter and boundary layouts; which of the two
 // a network takes is mlp_layer_by_layer(): a width outside 16/32/64/128, or -- at any width -- a hidden activation whose derivative needs
-// the pre-activation (SiLU, Sine), which the fused kernels do not keep.  What follows describes the fused kernels.
+// the pre-activation (SiLU, Sine), which the fused kernels do not keep, or more than MLP_MAX_OUT_WIDTH (padded) outputs, up to
+// MLP_GENERAL_MAX_OUT_WIDTH.  What follows describes the fused kernels.
 //
 // Restates the BEHAVIOUR of reference src/fully_fused_mlp.cu:499-837 (kernel_mlp_fused,
 // kernel_mlp_fused_backward and the four CUTLASS call sites :786,:820,:829,:835) -- not its tiling.
@@ -35,7 +36,7 @@ namespace tcnn_hip {
 struct MlpMeta {
 	uint32_t in_width;          // multiple of 16
 	uint32_t width;             // 16 / 32 / 64 / 128 (fused kernels), or any other multiple of 16 <= MLP_GENERAL_MAX_WIDTH (layer by layer)
-	uint32_t padded_out;        // multiple of 16, <= MLP_MAX_OUT_WIDTH
+	uint32_t padded_out;        // multiple of 16, <= MLP_MAX_OUT_WIDTH (fused kernels); above it, up to MLP_GENERAL_MAX_OUT_WIDTH: layer by layer
 	uint32_t n_hidden_matmuls;  // n_hidden_layers - 1
 	uint32_t activation;        // Activation of the hidden layers (SiLU / Sine: layer by layer at every width)
 	uint32_t output_activation; // Activation of the output layer (default None; never SiLU / Sine)
@@ -86,10 +87,13 @@ constexpr uint32_t MLP_MAX_OUT_WIDTH = 128;  // padded; more than 16 outputs tra
 // the layer-by-layer network of the other widths (mlp_general.hip)
 constexpr uint32_t MLP_GENERAL_MAX_WIDTH = 1024;
 constexpr uint32_t MLP_GENERAL_MAX_IN_WIDTH = 1024;
+constexpr uint32_t MLP_GENERAL_MAX_OUT_WIDTH = 1024;  // padded
 // the widths the fused kernels are instantiated for
 TCNN_HOST_DEVICE bool mlp_fused_width(uint32_t width) { return width == 16u || width == 32u || width == 64u || width == 128u; }
 // THE place that decides the path: true -> mlp_general.hip, and every fused kernel's *_supported predicate is false
-TCNN_HOST_DEVICE bool mlp_layer_by_layer(const MlpMeta& m) { return !mlp_fused_width(m.width) || act_needs_preactivation(m.activation); }
+TCNN_HOST_DEVICE bool mlp_layer_by_layer(const MlpMeta& m) {
+	return !mlp_fused_width(m.width) || act_needs_preactivation(m.activation) || m.padded_out > MLP_MAX_OUT_WIDTH;
+}
 // The stack a forward pass with `hidden != nullptr` writes and the backward pass reads: [n_hidden][n][W] post-activations; for an activation
 // that needs them, followed by [n_hidden][n][W] pre-activations.  Readers of post-activations (the next layer, the weight-gradient
 // products) address the first block either way.
@@ -182,6 +186,11 @@ struct MlpF32Output {
 void mlp_infer_wave(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, half_t* output, const MlpF32Output& f32 = {},
                     const MlpF32Input* f32_input = nullptr);  // f32_input (16-byte aligned, mlp_infer_f32_input_supported): `input` is ignored
 bool mlp_infer_f32_input_supported(const MlpMeta& m, uint32_t n);
+// Inference straight into the caller's fp32 matrix, by whichever kernel stores it itself: the register-resident inference kernel, or the
+// output layer of a layer-by-layer network (mlp_general.hip, the trimmed fp32 epilogue).  Bit-equal to mlp_forward into a padded 16-bit
+// matrix followed by trim_and_cast.  Throws where mlp_forward_f32_supported is false.
+bool mlp_forward_f32_supported(const MlpMeta& m, uint32_t n);
+void mlp_forward_f32(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, const MlpF32Output& f32);
 
 // number of fp32 slabs / loss partial sums mlp_train() writes for this shape and batch (<= mlp_backward_n_partials)
 uint32_t mlp_train_n_partials(const MlpMeta& m, uint32_t n, LossType loss);
@@ -198,7 +207,9 @@ void mlp_finalize_gradients(hipStream_t stream, const MlpMeta& m, uint32_t n_par
 // mlp_backward / mlp_backward_n_partials / mlp_backward_workspace_bytes route here by that predicate; same contracts.  With hidden == nullptr the
 // forward pass keeps two ping-pong activation matrices in stream-ordered scratch of its own.  No fused training pass: mlp_train_supported
 // is false for them, so a training step is forward (saved activations) -> loss -> backward.
-void mlp_general_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, half_t* hidden, half_t* output);
+// f32.out given: inference into the caller's fp32 matrix (`hidden` and `output` must be null)
+void mlp_general_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, half_t* hidden, half_t* output,
+                         const MlpF32Output& f32 = {});
 uint32_t mlp_general_n_partials(const MlpMeta& m, uint32_t n);
 size_t mlp_general_backward_workspace_bytes(const MlpMeta& m, uint32_t n);
 void mlp_general_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params_t, const half_t* input, const half_t* hidden,

@@ -1007,8 +1007,9 @@ static void check_meta(const MlpMeta& m, uint32_t n) {
 	if (m.in_width % 16 != 0 || m.in_width == 0 || m.in_width > max_in) {
 		throw std::runtime_error(std::string(fused ? "FullyFusedMLP" : "MLP") + ": input width must be a multiple of 16 and at most " + std::to_string(max_in) + ".");
 	}
-	if (m.padded_out % 16 != 0 || m.padded_out == 0 || m.padded_out > MLP_MAX_OUT_WIDTH) {
-		throw std::runtime_error(std::string(fused ? "FullyFusedMLP" : "MLP") + ": at most " + std::to_string(MLP_MAX_OUT_WIDTH) + " output dimensions are supported.");
+	const uint32_t max_out = fused ? MLP_MAX_OUT_WIDTH : MLP_GENERAL_MAX_OUT_WIDTH;
+	if (m.padded_out % 16 != 0 || m.padded_out == 0 || m.padded_out > max_out) {
+		throw std::runtime_error(std::string(fused ? "FullyFusedMLP" : "MLP") + ": at most " + std::to_string(max_out) + " output dimensions are supported.");
 	}
 	if (n % BATCH_SIZE_GRANULARITY != 0) throw std::runtime_error("Batch size must be a multiple of 256.");
 }
@@ -1050,6 +1051,20 @@ void mlp_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t*
 		case 64: launch_forward<64>(stream, m, n, params, input, hidden, output); break;
 		case 128: launch_forward<128>(stream, m, n, params, input, hidden, output); break;
 	}
+}
+
+bool mlp_forward_f32_supported(const MlpMeta& m, uint32_t n) { return mlp_layer_by_layer(m) || mlp_infer_wave_supported(m, n); }
+
+void mlp_forward_f32(hipStream_t stream, const MlpMeta& m, uint32_t n, const half_t* params, const half_t* input, const MlpF32Output& f32) {
+	check_meta(m, n);
+	if (n == 0) return;
+	if (!f32.out || f32.dims == 0 || f32.dims > m.padded_out) throw std::runtime_error("mlp_forward_f32: an fp32 output matrix of at most padded_out columns is required");
+	if (mlp_layer_by_layer(m)) {
+		mlp_general_forward(stream, m, n, params, input, nullptr, nullptr, f32);
+		return;
+	}
+	if (!mlp_infer_wave_supported(m, n)) throw std::runtime_error("mlp_forward_f32: no kernel stores fp32 for this network (check mlp_forward_f32_supported first)");
+	mlp_infer_wave(stream, m, n, params, input, nullptr, f32);
 }
 
 void mlp_transpose_weights(hipStream_t stream, const MlpMeta& m, const half_t* params, half_t* params_t) {

@@ -428,21 +428,21 @@ static NetworkDesc create_network_desc(uint32_t n_input_dims, uint32_t n_output_
 		throw std::runtime_error("Activation '" + out_act_name + "' is not supported as output_activation: output activations must be expressible from the output value "
 		                         "(the backward pass takes their derivative at the stored output; this one needs the pre-activation).");
 	}
+	// more than MLP_MAX_OUT_WIDTH (padded) outputs: layer by layer as well, under either spelling -- the reference's FullyFusedMLP hands a
+	// last layer of more than 16 outputs to a plain matrix product (fully_fused_mlp.cu:786), its CutlassMLP takes any width
 	d.mlp.width = n_neurons;
 	d.mlp.activation = (uint32_t)act;
+	d.mlp.padded_out = next_multiple(n_output_dims, 16u);  // fully_fused_mlp.cu:656
 	const bool fused = !mlp_layer_by_layer(d.mlp);
 	const char* const name = fused ? "FullyFusedMLP" : "CutlassMLP";
 	d.n_hidden_layers = net.value("n_hidden_layers", 5u);
 	if (d.n_hidden_layers == 0) throw std::runtime_error(std::string(name) + " requires at least 1 hidden layer (3 layers in total).");
 	d.n_output_dims = n_output_dims;
 	d.mlp.in_width = n_input_dims;
-	d.mlp.width = n_neurons;
-	d.mlp.padded_out = next_multiple(n_output_dims, 16u);  // fully_fused_mlp.cu:656
 	d.mlp.n_hidden_matmuls = d.n_hidden_layers - 1;
-	d.mlp.activation = (uint32_t)act;
 	d.mlp.output_activation = (uint32_t)out_act;
-	if (d.mlp.padded_out > MLP_MAX_OUT_WIDTH) {
-		throw std::runtime_error(std::string(name) + ": more than " + std::to_string(MLP_MAX_OUT_WIDTH) + " output dimensions are not supported by this build.");
+	if (d.mlp.padded_out > MLP_GENERAL_MAX_OUT_WIDTH) {
+		throw std::runtime_error(std::string(name) + ": more than " + std::to_string(MLP_GENERAL_MAX_OUT_WIDTH) + " output dimensions are not supported by this build.");
 	}
 	const uint32_t max_in = fused ? MLP_MAX_IN_WIDTH : MLP_GENERAL_MAX_IN_WIDTH;
 	if (n_input_dims % 16 != 0 || n_input_dims > max_in) {

@@ -236,18 +236,18 @@ void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, cons
 		hidden = ctx->hidden.as<half_t>();
 	}
 	ProfScope prof(profiler, stream, STAGE_MLP_FWD);
-	if (f32) {  // (inference_to_f32 below checked that the register-resident inference kernel takes this network)
-		mlp_infer_wave(stream, md.net.mlp, n, params, enc.as<half_t>(), nullptr, *f32);
+	if (f32) {  // (inference_to_f32 below checked that a kernel that stores fp32 itself takes this network)
+		mlp_forward_f32(stream, md.net.mlp, n, params, enc.as<half_t>(), *f32);
 		return;
 	}
 	mlp_forward(stream, md.net.mlp, n, params, enc.as<half_t>(), hidden, output);
 }
 
-// network->inference into the caller's fp32 matrix (object.h:214-271).  Where the register-resident inference kernel runs the network it
-// writes the fp32 elements itself; otherwise the padded 16-bit result goes through trim_and_cast as in the reference.
+// network->inference into the caller's fp32 matrix (object.h:214-271).  Where the register-resident inference kernel or the layer-by-layer
+// network runs it, the kernel writes the fp32 elements itself; otherwise the padded 16-bit result goes through trim_and_cast as in the reference.
 void inference_to_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const half_t* params, float* out, uint32_t stride_i, uint32_t stride_j) {
 	const uint32_t padded = md.padded_output_width(), width = md.output_width();
-	if (md.has_network && n > 0 && mlp_infer_wave_supported(md.net.mlp, n)) {
+	if (md.has_network && n > 0 && mlp_forward_f32_supported(md.net.mlp, n)) {
 		const MlpF32Output f32 = {out, width, stride_i, stride_j};
 		model_forward(stream, nullptr, md, layout, n, input, nullptr, params, nullptr, false, &f32);
 		return;
