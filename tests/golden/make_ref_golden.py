@@ -8,7 +8,10 @@ Contents: kernel_grid (encodings/grid.h:48-212) on the data/config_hash.json gri
 (src/fully_fused_mlp.cu:46-557; the arithmetic inside one 16x16x16 tensor-core operation is modelled, oracle/ref_shim/mma.h) on the
 bench's network and on BASELINE configs[1]'s.
 
-    python tests/golden/make_ref_golden.py
+tests/golden/reference_domain.npz (domain() below): kernel_grid on the same grid at positions outside the unit cube and on cell boundaries.
+
+    python tests/golden/make_ref_golden.py            # both files
+    python tests/golden/make_ref_golden.py domain     # reference_domain.npz only
 """
 import ctypes as C
 import os
@@ -99,5 +102,35 @@ def main():
     print("wrote reference_small.npz:", {k: v.shape for k, v in out.items()})
 
 
+def domain():
+    """tests/golden/reference_domain.npz: the reference's kernel_grid (encodings/grid.h:48-212) on 256 positions OUTSIDE the unit cube and on
+    cell boundaries (tests/grid_domain_positions.py), on the same 3-D data/config_hash.json grid with the same seeded table as above.
+    `dy_dx_first` holds all 256 rows: the special rows are spread over the whole batch."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import grid_domain_positions
+    assert build_ref.build(), "needs the reference tree (oracle/build_ref.py)"
+    R = C.CDLL(build_ref.LIB)
+    R.ref_log2_per_level_scale.restype = C.c_float
+    f32 = lambda v: C.c_float(float(v))  # noqa: E731
+    n, D, L, F, T, base, pls = 256, 3, 16, 2, 15, 16, 1.5
+    g = O.grid_init(D, L, F, T, base, pls)
+    positions = grid_domain_positions.for_grid(g, n, seed=1337)
+    u = np.zeros(g.n_params, np.float32)
+    R.ref_generate_random_uniform(C.c_uint64(42), C.c_uint64(0), C.c_size_t(g.n_params), p(u), f32(0.0), f32(1.0))
+    grid_h = O.f2h(np.float32(2.0) * u - np.float32(1.0))
+    offsets = (C.c_uint32 * (L + 1))(*[g.offsets[l] for l in range(L + 1)])
+    log2_pls = R.ref_log2_per_level_scale(f32(pls))
+    enc = np.zeros((L * F, n), np.uint16)
+    dy_dx = np.zeros((L * F, n, D), np.float32)
+    assert R.ref_grid_forward(D, F, n, L, offsets, base, f32(log2_pls), f32(1.0), 1, 0, p(grid_h), p(positions), p(enc), p(dy_dx)) == 0
+    out = dict(positions=positions, grid_seed=np.array([42]), encoded=np.ascontiguousarray(enc.T), dy_dx_first=np.ascontiguousarray(dy_dx.transpose(1, 0, 2)))
+    np.savez_compressed(os.path.join(os.path.dirname(os.path.abspath(__file__)), "reference_domain.npz"), **out)
+    print("wrote reference_domain.npz:", {k: v.shape for k, v in out.items()})
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["domain"]:  # python tests/golden/make_ref_golden.py domain: only reference_domain.npz
+        domain()
+    else:
+        main()
+        domain()

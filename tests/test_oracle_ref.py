@@ -37,8 +37,10 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import build_ref  # noqa: E402
 from oracle import oracle as O  # noqa: E402
+import grid_domain_positions  # noqa: E402
 
 _ref = None
 
@@ -88,7 +90,12 @@ def _ref_interp(i):  # common.h:178-182: Nearest, Linear, Smoothstep
     return {O.INTERP_NEAREST: 0, O.INTERP_LINEAR: 1, O.INTERP_SMOOTHSTEP: 2}[i]
 
 
-def _positions(n, d, seed):
+DOMAINS = ["unit", "hard"]  # [0, 1) as callers inside the cube pass it; tests/grid_domain_positions.py: outside the cube and on cell boundaries
+
+
+def _positions(n, d, seed, domain="unit", g=None):
+    if domain == "hard":
+        return grid_domain_positions.for_grid(g, n, seed)
     rng = np.random.default_rng(seed)
     x = rng.random((n, d), dtype=np.float32)
     x[0] = 0.0                      # the cell corners themselves
@@ -107,8 +114,7 @@ def test_manifest_names_what_was_compiled():
     assert "include/tiny-cuda-nn/common_device.h" in m["whole_files"]
 
 
-@pytest.mark.parametrize("case", GRID_CASES)
-def test_level_scales_resolutions_and_indices(case):
+def _check_level_scales_resolutions_and_indices(case, domain):
     """The oracle's per-level table and corner indices == the reference's grid_scale / grid_resolution / grid_index."""
     g, R = _grid(case), ref()
     D, F, L, T, base, pls, gtype, interp = case
@@ -118,9 +124,9 @@ def test_level_scales_resolutions_and_indices(case):
         R.ref_grid_level(l, f32(log2_pls), base, C.byref(s), C.byref(r))
         assert np.float32(s.value) == np.float32(g.scale[l]) and r.value == g.resolution[l], (l, s.value, g.scale[l])
     # corner indices of random samples, every level: oracle's orc_grid_indices vs grid_index on the cell the reference's pos_fract finds
-    x = _positions(257, D, seed=3)
+    x = _positions(257, D, 3, domain, g)
     idx = O.grid_indices(g, x)
-    for i in range(0, x.shape[0], 7):
+    for i in range(0, x.shape[0], 7 if domain == "unit" else 1):  # (hard: every row is there for a reason)
         for l in range(L):
             cell = []
             for d in range(D):
@@ -136,14 +142,13 @@ def test_level_scales_resolutions_and_indices(case):
                 assert idx[i, l, c] == want, (i, l, c)
 
 
-@pytest.mark.parametrize("case", GRID_CASES)
-def test_grid_forward_and_dy_dx_bit_exact(case):
+def _check_grid_forward_and_dy_dx_bit_exact(case, domain):
     g, R = _grid(case), ref()
     D, F, L, T, base, pls, gtype, interp = case
     n = 1024 + 5  # not a multiple of the 512-thread blocks
     rng = np.random.default_rng(11)
     params = O.f2h((rng.standard_normal(g.n_params) * 0.3).astype(np.float32))
-    x = _positions(n, D, seed=5)
+    x = _positions(n, D, 5, domain, g)
     out, dy_dx = O.grid_forward(g, params, x, want_dy_dx=True)  # [n][L*F] half bits, [n][L*F][D]
     offsets = (C.c_uint32 * (L + 1))(*[g.offsets[l] for l in range(L + 1)])
     log2_pls = R.ref_log2_per_level_scale(f32(pls))
@@ -154,8 +159,7 @@ def test_grid_forward_and_dy_dx_bit_exact(case):
     assert np.array_equal(dy_dx, dyr.transpose(1, 0, 2))
 
 
-@pytest.mark.parametrize("case", GRID_CASES)
-def test_grid_backward_records_and_sums(case):
+def _check_grid_backward_records_and_sums(case, domain):
     """kernel_grid_backward adds (GRAD_T)weight * grad per corner with atomics (fp16 for F >= 2, fp32 for F == 1).  The oracle sums the
     same records exactly (float64).  Entries hit exactly once must agree bit for bit after one rounding; the others to the error of
     the reference's own running fp16 sum."""
@@ -163,7 +167,7 @@ def test_grid_backward_records_and_sums(case):
     D, F, L, T, base, pls, gtype, interp = case
     n = 512 + 3
     rng = np.random.default_rng(17)
-    x = _positions(n, D, seed=9)
+    x = _positions(n, D, 9, domain, g)
     dy = O.f2h((rng.standard_normal((n, L * F)) * 0.05).astype(np.float32))
     want = O.grid_backward(g, x, dy)  # float64 [n_params]
     offsets = (C.c_uint32 * (L + 1))(*[g.offsets[l] for l in range(L + 1)])
@@ -183,7 +187,8 @@ def test_grid_backward_records_and_sums(case):
         np.add.at(hits, g.offsets[l] + idx[:, l, :corners].reshape(-1), 1)
     hits = np.repeat(hits, F)
     once = hits == 1
-    assert once.sum() > 40
+    # (hard: four times the area folds onto the same table, so the small tiled tables keep only a handful of entries that are hit once)
+    assert once.sum() > (40 if domain == "unit" else 0)
     if F == 1:
         assert np.array_equal(got[once].astype(np.float32), want[once].astype(np.float32))
     else:
@@ -196,13 +201,13 @@ def test_grid_backward_records_and_sums(case):
     assert np.all(np.abs(got[many] - want[many]) <= hits[many] * (2.0 ** -11 if F > 1 else 2.0 ** -24) * magnitude[many] * 1.001)
 
 
-def test_grid_backward_input_bit_exact():
+def _check_grid_backward_input_bit_exact(domain):
     g, R = _grid(GRID_CASES[0]), ref()
     D, F, L = 3, 2, 16
     n = 300
     rng = np.random.default_rng(23)
     params = O.f2h((rng.standard_normal(g.n_params) * 0.3).astype(np.float32))
-    x = _positions(n, D, seed=2)
+    x = _positions(n, D, 2, domain, g)
     _, dy_dx = O.grid_forward(g, params, x, want_dy_dx=True)
     dy = O.f2h((rng.standard_normal((n, L * F)) * 0.05).astype(np.float32))
     want = O.grid_backward_input(g, dy, dy_dx)
@@ -211,8 +216,7 @@ def test_grid_backward_input_bit_exact():
     assert np.array_equal(got, want)
 
 
-@pytest.mark.parametrize("case", GRID_CASES)
-def test_grid_fp32_instantiation(case):
+def _check_grid_fp32_instantiation(case, domain):
     """GridEncodingTemplated<float> -- what create_encoding(..., Precision::Fp32) builds (cpp_api.cu:165-168): the reference's kernel_grid,
     kernel_grid_backward and kernel_grid_backward_input instantiated with T = float against the oracle's fp32 restatement.  Features,
     dy_dx and the input gradient bit for bit; parameter gradients: entries hit once bit for bit, the others to the rounding of the
@@ -222,7 +226,7 @@ def test_grid_fp32_instantiation(case):
     n = 512 + 3
     rng = np.random.default_rng(31)
     params = (rng.standard_normal(g.n_params) * 0.3).astype(np.float32)
-    x = _positions(n, D, seed=6)
+    x = _positions(n, D, 6, domain, g)
     out, dy_dx = O.grid_forward_f32(g, params, x, want_dy_dx=True)
     offsets = (C.c_uint32 * (L + 1))(*[g.offsets[l] for l in range(L + 1)])
     log2_pls = R.ref_log2_per_level_scale(f32(pls))
@@ -255,8 +259,7 @@ def test_grid_fp32_instantiation(case):
         assert np.array_equal(got_dx, want_dx)
 
 
-@pytest.mark.parametrize("case", GRID_CASES)
-def test_grid_second_order_kernels(case):
+def _check_grid_second_order_kernels(case, domain):
     """kernel_grid_backward_input_backward_grid / _backward_input / _backward_dLdoutput (grid.h:351-653) as backward_backward_input_impl
     launches them (grid.h:907-1042).  dL_ddLdy is one fp32 dot product per (sample, feature): bit-exact.  dL_dx is an fp32 atomicAdd per
     (level, feature pair) and the grid gradient an atomic sum in its accumulation type (fp16 for F >= 2): the same records, summed in
@@ -265,7 +268,7 @@ def test_grid_second_order_kernels(case):
     D, F, L, T, base, pls, gtype, interp = case
     n = 300
     rng = np.random.default_rng(5)
-    x = _positions(n, D, seed=4)
+    x = _positions(n, D, 4, domain, g)
     params = O.f2h((rng.standard_normal(g.n_params) * 0.3).astype(np.float32))
     ddx = (rng.standard_normal((n, D)) * 1e-3).astype(np.float32)  # times the level's scale (up to 2^19): the records must stay inside fp16
     dy = O.f2h((rng.standard_normal((n, L * F)) * 0.05).astype(np.float32))
@@ -289,6 +292,67 @@ def test_grid_second_order_kernels(case):
     assert np.abs(dx - want_dx).max() <= 2e-6 * np.abs(want_dx).max()
     assert np.linalg.norm(grad - want_grad) <= (1e-6 if F == 1 else 2e-3) * np.linalg.norm(want_grad)
     assert np.array_equal(grad == 0, want_grad == 0) or F > 1  # untouched entries stay zero
+
+
+# Each grid check above runs on both position sets with the same bars: on [0, 1) under the name it always had, and on
+# tests/grid_domain_positions.py's positions outside the unit cube and on cell boundaries (cells that wrap modulo 2^32, common_device.h:1016-1043),
+# where ref_pos_fract / ref_grid_index are the ground truth for the wrap.
+@pytest.mark.parametrize("case", GRID_CASES)
+def test_level_scales_resolutions_and_indices(case):
+    _check_level_scales_resolutions_and_indices(case, "unit")
+
+
+@pytest.mark.parametrize("case", GRID_CASES)
+def test_level_scales_resolutions_and_indices_outside_the_unit_cube(case):
+    _check_level_scales_resolutions_and_indices(case, "hard")
+
+
+@pytest.mark.parametrize("case", GRID_CASES)
+def test_grid_forward_and_dy_dx_bit_exact(case):
+    _check_grid_forward_and_dy_dx_bit_exact(case, "unit")
+
+
+@pytest.mark.parametrize("case", GRID_CASES)
+def test_grid_forward_and_dy_dx_bit_exact_outside_the_unit_cube(case):
+    _check_grid_forward_and_dy_dx_bit_exact(case, "hard")
+
+
+@pytest.mark.parametrize("case", GRID_CASES)
+def test_grid_backward_records_and_sums(case):
+    _check_grid_backward_records_and_sums(case, "unit")
+
+
+@pytest.mark.parametrize("case", GRID_CASES)
+def test_grid_backward_records_and_sums_outside_the_unit_cube(case):
+    _check_grid_backward_records_and_sums(case, "hard")
+
+
+def test_grid_backward_input_bit_exact():
+    _check_grid_backward_input_bit_exact("unit")
+
+
+def test_grid_backward_input_bit_exact_outside_the_unit_cube():
+    _check_grid_backward_input_bit_exact("hard")
+
+
+@pytest.mark.parametrize("case", GRID_CASES)
+def test_grid_fp32_instantiation(case):
+    _check_grid_fp32_instantiation(case, "unit")
+
+
+@pytest.mark.parametrize("case", GRID_CASES)
+def test_grid_fp32_instantiation_outside_the_unit_cube(case):
+    _check_grid_fp32_instantiation(case, "hard")
+
+
+@pytest.mark.parametrize("case", GRID_CASES)
+def test_grid_second_order_kernels(case):
+    _check_grid_second_order_kernels(case, "unit")
+
+
+@pytest.mark.parametrize("case", GRID_CASES)
+def test_grid_second_order_kernels_outside_the_unit_cube(case):
+    _check_grid_second_order_kernels(case, "hard")
 
 
 def test_frequency_encoding_bit_exact():
@@ -656,6 +720,19 @@ def test_oracle_reproduces_the_reference_made_fixture():
         O.adam_step(h, 1024, 128.0, step, st["w"], st["h"], gold[f"adam_grad{step}"], st["m1"], st["m2"], st["s"])
     for k, name in (("w", "adam_w"), ("h", "adam_h"), ("m1", "adam_m1"), ("m2", "adam_m2"), ("s", "adam_steps")):
         assert np.array_equal(st[k], gold[name]), name
+
+
+def test_oracle_reproduces_the_reference_made_domain_fixture():
+    """tests/golden/reference_domain.npz: the reference's kernel_grid on 256 positions outside the unit cube and on cell boundaries
+    (tests/golden/make_ref_golden.py domain()).  The positions are the generator's, the features and dy_dx the oracle's bit for bit."""
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "reference_domain.npz"))
+    g, grid_h = golden_inputs(gold)
+    x = gold["positions"]
+    assert np.array_equal(grid_domain_positions.for_grid(g, x.shape[0], seed=1337).view(np.uint32), x.view(np.uint32))
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "reference_domain.npz")) <= os.path.getsize(os.path.join(ROOT, "tests", "golden", "reference_small.npz"))
+    enc, dy_dx = O.grid_forward(g, grid_h, x, want_dy_dx=True)
+    assert np.array_equal(enc, gold["encoded"])
+    assert np.array_equal(dy_dx[:gold["dy_dx_first"].shape[0]], gold["dy_dx_first"])
 
 
 @pytest.mark.parametrize("tag,in_w,out_w", [("net_a", 32, 4), ("net_b", 64, 16)])

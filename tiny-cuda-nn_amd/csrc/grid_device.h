@@ -1,6 +1,12 @@
 // grid_device.h -- what every pass of the grid encoding shares: the level / cell arithmetic (bit-exact against the CPU oracle: build with
 // -ffp-contract=off, the fp32 position / weight arithmetic must round exactly as written), the one statement of each per-level fact, and the
 // D x F dispatch of the launchers.  See grid_kernels.h for the API and the reference lines restated.
+//
+// Input domain: positions need not lie in [0, 1).  Any finite x with |x| * scale + 0.5 < 2^31 at every level behaves as the reference's
+// pos_fract does (common_device.h:1016-1043): cell coordinates wrap modulo 2^32 (cell -1 is 0xFFFFFFFF), are hashed or taken modulo the table
+// size, and the weights come from the fraction; nothing is clamped, and every shortcut on top of make_cell (hhi = hlo + prime, the pair tag of
+// the record scatter, the dense i1 = i0 + 1) holds for wrapped cells (tests/grid_domain_positions.py, tests/test_emu_grid_domain.py).  NaN, Inf
+// and larger magnitudes are unspecified, as in the reference: its float -> int conversion is undefined there.
 #pragma once
 #include "grid_kernels.h"
 
