@@ -395,6 +395,12 @@ int tcnn_trainer_set_lds_level_budget(tcnn_trainable_model_t* tm, uint32_t bytes
  * Also selectable with TCNN_GRID_BACKWARD=sliced_f32|sliced_f16|atomic|bucketed. */
 int tcnn_set_grid_backward_mode(int mode);
 int tcnn_get_grid_backward_mode(void);
+/* Second-order pass (tcnn_module_backward_backward_input) of an fp32 grid encoding, process-wide: 0 = computed in fp32 from the caller's fp32
+ * tensors (default: the reference's T = float kernels; the parameter gradient is one fp32 global atomic per corner and feature), 1 = the 16-bit
+ * kernels on stand-ins of the caller's tensors (parameters rounded to 16 bits, dL_doutput scaled by a power of two <= 1024 and rounded to 16
+ * bits, results widened; its parameter scatter is the bucketed pass -- A/B timing, tests).  Other modules are not affected. */
+int tcnn_set_fp32_second_order(int mode);
+int tcnn_get_fp32_second_order(void);
 /* Accumulator form of the bucket owners in mode 3, process-wide (same bits from all three): 0 = packed (default: both features of a
  * payload word in one 64-bit LDS word, half the LDS atomics and half the LDS; slices whose sums could leave int32 are redone wide),
  * 1 = 64-bit fixed point per value throughout, 2 = the packed kernel with every slice through its wide redo (tests). */

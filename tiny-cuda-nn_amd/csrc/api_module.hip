@@ -15,14 +15,15 @@ struct tcnn_module {
 	uint32_t lds_level_budget = 0;  // 0: default LDS slice size of the sliced grid backward
 	// create_encoding(..., Precision::Fp32) (cpp_api.cu:165-174 -> Encoding<float>): parameters, outputs and gradients are fp32 and the
 	// first-order passes COMPUTE in fp32 (encoding_forward_f32 / encoding_backward_f32: the grid's kernel_grid<float> formulation, fp32
-	// global atomics for its parameter gradients; frequency / one-blob / identity with float values).  Only the second-order pass
-	// (backward_backward_input, grid only) still goes through 16-bit stand-ins of the caller's tensors: incoming gradients are scaled
+	// global atomics for its parameter gradients; frequency / one-blob / identity with float values).  So does the second-order pass
+	// (backward_backward_input, grid only): the T = float instances of the reference's three kernels on the caller's own tensors.
+	// tcnn_set_fp32_second_order(1) brings back the 16-bit stand-ins it used to run on (A/B runs, tests): incoming gradients are scaled
 	// into that type's range by the largest power of two <= FP32_GRADIENT_SCALE that keeps max |dL_doutput| * scale <=
 	// FP32_GRADIENT_TARGET (found on the device per call) and the results scaled back, exactly.
 	bool fp32_io = false;
 };
 static constexpr float FP32_GRADIENT_SCALE = 1024.0f, FP32_GRADIENT_TARGET = 16384.0f;
-// the 16-bit copies an fp32 module works on
+// the 16-bit copies an fp32 module works on with tcnn_set_fp32_second_order(1)
 struct Fp32Bridge {
 	Scratch params, output, dL_doutput, dL_dparams;
 	static Scratch to_half(hipStream_t stream, const void* src, size_t n, float scale = 1.0f) {
@@ -138,12 +139,14 @@ int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_,
 	hipStream_t stream = (hipStream_t)stream_;
 	const Model& md = m->md;
 	const EncodingDesc& e = md.enc;
-	// fp32 module: 16-bit stand-ins for the caller's fp32 tensors (see tcnn_module::fp32_io)
+	// fp32 module with tcnn_set_fp32_second_order(1): 16-bit stand-ins for the caller's fp32 tensors (see tcnn_module::fp32_io)
+	const bool fp32_kernels = m->fp32_io && g_fp32_second_order.load() == 0;
+	const bool stand_ins = m->fp32_io && !fp32_kernels;
 	Scratch dy16, p16, dp16, ddy16, gscale;
 	void* const dL_dparams_f32 = dL_dparams;
 	void* const dL_ddLdoutput_f32 = dL_ddLdoutput;
 	const size_t n_out_elems = (size_t)n * e.padded_output_width;
-	if (m->fp32_io) {
+	if (stand_ins) {
 		if (dL_doutput) {
 			dy16 = Fp32Bridge::gradient_to_half(stream, dL_doutput, n_out_elems, gscale);
 			dL_doutput = dy16.ptr;
@@ -168,6 +171,20 @@ int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_,
 	io.ddx = dL_ddLdinput;
 	io.ddx_stride_i = md.n_input_dims;
 	io.ddx_stride_d = 1u;
+	if (fp32_kernels) {  // the caller's fp32 tensors as they are: no stand-ins, no gradient scale, no 16-bit scratch
+		if (dL_ddLdoutput) {  // grid.h:1012-1035
+			if (!ctx->ctx.dy_dx.ptr) throw std::runtime_error("backward_backward_input: the forward pass did not prepare input gradients");
+			grid_backward_backward_dLdoutput(stream, md.n_input_dims, e.n_output_dims, e.padded_output_width - e.n_output_dims, io, ctx->ctx.dy_dx.as<float>(),
+			                                 (float*)dL_ddLdoutput);
+		}
+		if ((dL_dparams || dL_dinput) && !dL_doutput) throw std::runtime_error("backward_backward_input: dL_doutput is required for parameter / input gradients");
+		if (dL_dparams && e.n_params > 0) grid_backward_f32(stream, grid, io, (const float*)dL_doutput, (float*)dL_dparams, false);  // grid.h:942-975, GradientMode::Overwrite
+		if (dL_dinput) {  // grid.h:977-1010
+			if (!params) throw std::runtime_error("backward_backward_input: params are required for the input gradient");
+			grid_backward_backward_input_f32(stream, grid, io, (const float*)dL_doutput, (const float*)params, dL_dinput, md.n_input_dims, 1u);
+		}
+		return TCNN_OK;
+	}
 	if (dL_ddLdoutput) {  // grid.h:1012-1035
 		if (!ctx->ctx.dy_dx.ptr) throw std::runtime_error("backward_backward_input: the forward pass did not prepare input gradients");
 		grid_backward_backward_dLdoutput(stream, md.n_input_dims, e.n_output_dims, e.padded_output_width - e.n_output_dims, io, ctx->ctx.dy_dx.as<float>(),
@@ -191,7 +208,7 @@ int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_,
 	if (dL_dinput) {  // grid.h:977-1010
 		grid_backward_backward_input(stream, grid, io, (const half_t*)dL_doutput, (const half_t*)params, dL_dinput, md.n_input_dims, 1u);
 	}
-	if (m->fp32_io) {  // dL_ddLdoutput does not depend on dL_doutput; the other two carry its scale
+	if (stand_ins) {  // dL_ddLdoutput does not depend on dL_doutput; the other two carry its scale
 		if (dL_ddLdoutput_f32) cast_f16_to_f32(stream, n_out_elems, ddy16.as<half_t>(), (float*)dL_ddLdoutput_f32);
 		if (dL_dparams_f32) {
 			if (gscale.ptr) cast_scaled_f16_to_f32(stream, md.n_params(), dp16.as<half_t>(), (float*)dL_dparams_f32, (const float*)(gscale.as<float>() + 1));

@@ -40,6 +40,7 @@ std::atomic<int> g_grid_backward_mode{initial_grid_backward_mode()};
 std::atomic<int> g_fused_network_passes{1};
 std::atomic<int> g_fused_identity_input{1};
 std::atomic<int> g_finalize_in_optimizer{1};
+std::atomic<int> g_fp32_second_order{0};
 
 }  // namespace tcnn_hip
 
@@ -152,6 +153,12 @@ int tcnn_get_grid_backward_mode(void) { return g_grid_backward_mode.load(); }
 int tcnn_set_grid_backward_mode(int mode) {
 	if (mode < 0 || mode > 3) return TCNN_ERROR;
 	g_grid_backward_mode.store(mode);
+	return TCNN_OK;
+}
+int tcnn_get_fp32_second_order(void) { return g_fp32_second_order.load(); }
+int tcnn_set_fp32_second_order(int mode) {
+	if (mode < 0 || mode > 1) return TCNN_ERROR;
+	g_fp32_second_order.store(mode);
 	return TCNN_OK;
 }
 

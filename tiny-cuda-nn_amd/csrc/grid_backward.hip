@@ -73,19 +73,29 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_backward_atomic_f32(const
 	if (!io.max_level && level_is_off<false>(meta, level, F)) return;
 	const Level<D> lv = make_level<D>(meta, level);
 	float* __restrict__ grad = grid_gradient + (size_t)meta.offset[level] * F;
+	const bool second_order = io.ddx != nullptr;  // kernel_grid_backward_input_backward_grid<float, float> (grid.h:427-455): another corner weight
 	for (uint32_t s = 0; s < GRID_SPT; ++s) {
 		const uint32_t i = tile * GRID_TILE + s * GRID_THREADS + threadIdx.x;
 		if (i >= io.n) continue;
 		if (io.max_level && level_is_off<false>(meta, io, i, level, F)) continue;
-		Cell<D> c = make_cell<D, false>(lv, io, i);
+		float x[D];
+		load_position<D>(io, i, x);
+		Cell<D> c = make_cell<D, false>(lv, x);
 		float g[F];
 #pragma unroll
 		for (uint32_t f = 0; f < F; ++f) g[f] = dL_dy[(size_t)(level * F + f) * io.stride_k + (size_t)i * io.stride_i];
-		const bool one_corner = lv.nearest || meta.stochastic != 0u;
-		if (meta.stochastic != 0u && !lv.nearest) pick_stochastic_corner<D>(c, i, level, io.n);
+		float dd[D];
+#pragma unroll
+		for (uint32_t d = 0; d < D; ++d) dd[d] = 0.0f;
+		if (second_order) {
+			load_ddx<D>(io, i, dd);
+			second_order_weights_f32<D>(lv, x, c);
+		}
+		const bool one_corner = !second_order && (lv.nearest || meta.stochastic != 0u);
+		if (!second_order && meta.stochastic != 0u && !lv.nearest) pick_stochastic_corner<D>(c, i, level, io.n);
 		const uint32_t n_corners = one_corner ? 1u : (1u << D);
 		for (uint32_t idx = 0; idx < n_corners; ++idx) {
-			const float weight = one_corner ? 1.0f : corner_weight<D>(c, idx);
+			const float weight = one_corner ? 1.0f : (second_order ? corner_weight_second_order<D>(lv, c, idx, dd) : corner_weight<D>(c, idx));
 			const uint32_t index = corner_index<D, false>(lv, c, idx);
 #pragma unroll
 			for (uint32_t f = 0; f < F; ++f) atomic_add_f32(grad + (size_t)index * F + f, weight * g[f]);  // (T)weight * grad, T = float (grid.h:254)
@@ -436,6 +446,8 @@ void grid_backward_f32(hipStream_t stream, const GridMeta& meta, const GridIO& i
 	if (!accumulate) {  // grid.h:865-867
 		if (hipMemsetAsync(grid_gradient, 0, n_params * sizeof(float), stream) != hipSuccess) throw std::runtime_error("grid_backward: memset failed");
 	}
+	// second-order scatter (io.ddx set): d(dy_dx)/d(grid) == 0 without interpolation (grid.h:422-425)
+	if (io.ddx && meta.interp == (uint32_t)InterpolationType::Nearest) return;
 	const uint32_t blocks = grid_n_blocks(meta.n_levels, io.n);
 	grid_dispatch(meta, [&](auto D, auto F) { TCNN_LAUNCH((k_grid_backward_atomic_f32<D, F>), dim3(blocks), dim3(GRID_THREADS), 0, stream, meta, io, dL_dy, grid_gradient); });
 }

@@ -208,6 +208,19 @@ TCNN_DEVICE float corner_weight_second_order(const Level<D>& lv, const Cell<D>& 
 	}
 	return total;
 }
+// fp32 encodings, second order: Smoothstep's lower weight as S(1 - t), which equals 1 - S(t).  make_cell's 1 - S(t) (the reference's form,
+// kept where results are held bit for bit) subtracts a ROUNDED S(t) and loses its relative accuracy as t -> 1; 1 - t is one rounding of the
+// exact fraction and S of it carries a few more, whatever its size.  Linear's 1 - t is left as it is.
+template <uint32_t D>
+TCNN_DEVICE void second_order_weights_f32(const Level<D>& lv, const float (&x)[D], Cell<D>& c) {
+	if (!lv.smooth) return;
+#pragma unroll
+	for (uint32_t d = 0; d < D; ++d) {
+		float p = __builtin_fmaf(lv.scale, x[d], 0.5f);
+		p -= __builtin_floorf(p);
+		c.w[d][0] = smoothstep(1.0f - p);
+	}
+}
 template <uint32_t D>
 TCNN_DEVICE void load_ddx(const GridIO& io, uint32_t i, float (&v)[D]) {
 #pragma unroll
@@ -232,6 +245,27 @@ TCNN_DEVICE void load_features(const half_t* p, h2 (&v)[(F + 1) / 2]) {
 		v[1] = h2{t[2], t[3]};
 		v[2] = h2{t[4], t[5]};
 		v[3] = h2{t[6], t[7]};
+	}
+}
+
+// F floats at `p` (an fp32 table: entries are F * 4 bytes apart, so the entry's own alignment holds) -> v; one 8-byte load at F == 2, 16-byte
+// loads from F == 4 on
+template <uint32_t F>
+TCNN_DEVICE void load_features(const float* p, float (&v)[F]) {
+	if constexpr (F == 1) {
+		v[0] = p[0];
+	} else if constexpr (F == 2) {
+		const f2 t = *(const f2*)p;
+		v[0] = t[0];
+		v[1] = t[1];
+	} else {
+		static_assert(F == 4 || F == 8, "n_features_per_level must be 1, 2, 4 or 8 (grid.h:1811-1821)");
+#pragma unroll
+		for (uint32_t q = 0; q < F / 4; ++q) {
+			const f4 t = *(const f4*)(p + 4 * q);
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j) v[4 * q + j] = t[j];
+		}
 	}
 }
 

@@ -117,6 +117,12 @@ void grid_backward_backward_dLdoutput(hipStream_t stream, uint32_t n_dims, uint3
                                       const float* dy_dx, half_t* dL_ddLdy);
 void grid_backward_backward_input(hipStream_t stream, const GridMeta& meta, const GridIO& io, const half_t* dL_dy, const half_t* params,
                                   float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_d);
+// The same three for an fp32 encoding (the reference's T = float instances of these kernels): fp32 parameters, dL_dy and results, nothing
+// rounded through 16 bits.  The parameter part is grid_backward_f32() with io.ddx set (one fp32 global atomic per corner and feature).
+void grid_backward_backward_dLdoutput(hipStream_t stream, uint32_t n_dims, uint32_t n_features, uint32_t n_to_pad, const GridIO& io, const float* dy_dx,
+                                      float* dL_ddLdy);
+void grid_backward_backward_input_f32(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, const float* params, float* dL_dx,
+                                      uint32_t dx_stride_i, uint32_t dx_stride_d);
 
 // Debug/parity helper: entry index per (sample, level, corner) -> indices[(i*L + l)*2^D + c]
 void grid_indices(hipStream_t stream, const GridMeta& meta, const GridIO& io, uint32_t* indices);

@@ -22,5 +22,8 @@ extern std::atomic<int> g_fused_identity_input;
 // training_step(run_optimizer = 1) on one GPU sums the network kernel's weight-gradient slabs inside the optimizer's launch (AdamFinalize);
 // tcnn_set_finalize_in_optimizer(0): always k_mlp_finalize_gradients, a launch of its own behind the network kernel (A/B runs, tests)
 extern std::atomic<int> g_finalize_in_optimizer;
+// second-order pass of an fp32 grid encoding: 0 = the fp32 kernels (default), 1 = the 16-bit kernels on stand-ins of the caller's fp32 tensors
+// (tcnn_set_fp32_second_order; A/B runs, tests)
+extern std::atomic<int> g_fp32_second_order;
 
 }  // namespace tcnn_hip

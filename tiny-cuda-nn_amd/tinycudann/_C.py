@@ -191,6 +191,8 @@ _sig("tcnn_set_finalize_in_optimizer", _i, _i)
 _sig("tcnn_set_fused_identity_input", _i, _i)
 _sig("tcnn_set_grid_backward_mode", _i, _i)
 _sig("tcnn_get_grid_backward_mode", _i)
+_sig("tcnn_set_fp32_second_order", _i, _i)
+_sig("tcnn_get_fp32_second_order", _i)
 _sig("tcnn_set_grid_owner_mode", _i, _i)
 _sig("tcnn_get_grid_owner_mode", _i)
 _sig("tcnn_grid_owner_wide_slices", _i, C.POINTER(C.c_uint64))
@@ -292,6 +294,17 @@ def get_grid_backward_mode():
 def set_grid_backward_mode(mode):
     """0: owner-computes LDS slices (fp32 accumulate, default); 1: same, packed fp16; 2: global atomics (A/B)."""
     _check(_lib.tcnn_set_grid_backward_mode(int(mode)))
+
+
+def get_fp32_second_order():
+    return int(_lib.tcnn_get_fp32_second_order())
+
+
+def set_fp32_second_order(mode):
+    """Second-order pass of an fp32 grid encoding, process-wide (both bindings call the same library): 0 the fp32 kernels (default), 1 the
+    16-bit kernels on stand-ins of the caller's fp32 tensors (A/B timing, tests)."""
+    if _lib.tcnn_set_fp32_second_order(int(mode)) != OK:
+        raise RuntimeError("set_fp32_second_order: mode must be 0 or 1")
 
 
 def get_grid_owner_mode():
