@@ -51,6 +51,42 @@ TCNN_DEVICE int to_fixed32(float v, const OwnerScale& sc) {
 	return r;
 #endif
 }
+// IEEE half, packed table: both values of a payload word times 2^24 as fp32 -- v_fma_mix_f32 converts the 16-bit source and multiplies in
+// ONE instruction (v_cvt_f32_f16 + v_mul_f32 before; exact either way: a power of two times at most 11 significant bits.  The fused add of
+// +0 turns a product of -0 into +0, which neither the integer conversion nor the bound's absolute value can tell apart).
+TCNN_DEVICE void half_pair_times_2_24(uint32_t word, float& s0, float& s1) {
+#if defined(TCNN_HOST_EMU) || defined(TCNN_BF16)
+	const h2 v = bits_h2(word);
+	s0 = (float)v[0] * 16777216.0f;
+	s1 = (float)v[1] * 16777216.0f;
+#else
+	const float two_24 = 16777216.0f;
+	asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(s0) : "v"(word), "v"(two_24));
+	asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(s1) : "v"(word), "v"(two_24));
+#endif
+}
+// total += |s|: the absolute value as a source modifier of the add (the compiler clears the sign bits of a pair with two v_and_b32 to feed
+// one packed add: three instructions for what two do)
+TCNN_DEVICE void add_abs(float& total, float s) {
+#if defined(TCNN_HOST_EMU)
+	total += __builtin_fabsf(s);
+#else
+	asm("v_add_f32_e64 %0, %0, |%1|" : "+v"(total) : "v"(s));
+#endif
+}
+// the truncating, saturating conversion of to_fixed32() alone, for a value that is an integer already
+TCNN_DEVICE int fixed32_of_scaled(float s) {
+#if defined(TCNN_HOST_EMU)
+	if (s != s) return 0;
+	if (s >= 2147483648.0f) return 2147483647;
+	if (s <= -2147483648.0f) return -2147483647 - 1;
+	return (int)s;
+#else
+	int r;
+	asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(s));
+	return r;
+#endif
+}
 template <uint32_t D, uint32_t F, uint32_t THREADS>
 TCNN_DEVICE void bucket_level_packed(const GridMeta& meta, const Level<D>& lv, uint32_t level, uint32_t bucket, uint32_t chunk,
                                      const OwnerSlice& own, uint32_t* __restrict__ counters, const uint32_t* queues,
@@ -164,10 +200,15 @@ TCNN_DEVICE void bucket_level_packed(const GridMeta& meta, const Level<D>& lv, u
 	// the same through the hand-pipelined halves (first pass over the queue only; its first two halves were requested above)
 	auto stream_pipelined = [&](auto&& add) {
 #if !defined(TCNN_HOST_EMU)
-		auto add_half = [&](uint32_t first, const rec3_t (&h)[4]) {
+		// WHOLE: every record of the round exists (all rounds but a lane's last, by the loop's own condition): no test against the count
+		// per record.  (The loop stays ONE copy: instantiated per table kind behind a branch, so that the second entry's index needs no
+		// scalar branch per record, the compiler copied registers of loads still in flight on the way into the copies --
+		// scripts/check_asm_load_hazard.py flagged it, and the GPU gave wrong sums.)
+		auto add_half = [&](auto whole_tag, uint32_t first, const rec3_t (&h)[4]) {
+			constexpr bool WHOLE = decltype(whole_tag)::value;
 #pragma unroll
 			for (uint32_t u = 0; u < 4; ++u) {
-				if (first + u * THREADS >= count) continue;
+				if (!WHOLE && first + u * THREADS >= count) continue;
 				const uint32_t rec[3] = {h[u][0], h[u][1], h[u][2]};
 				add(rec[0] & PAIR_INDEX_MASK, &rec[1]);
 				if (rec[0] & PAIR_HAS_SECOND) add(pair_second_index<D>(lv, rec[0]), &rec[1 + PW]);
@@ -182,7 +223,7 @@ TCNN_DEVICE void bucket_level_packed(const GridMeta& meta, const Level<D>& lv, u
 #pragma unroll
 			for (uint32_t k = 0; k < NG; ++k) {
 				await_oldest_group(grp[k]);
-				add_half(first + 4u * k * THREADS, grp[k]);
+				add_half(std::true_type{}, first + 4u * k * THREADS, grp[k]);
 				issue_half(grp[k], first + 4u * (NG + k) * THREADS, last);
 			}
 		}
@@ -190,7 +231,7 @@ TCNN_DEVICE void bucket_level_packed(const GridMeta& meta, const Level<D>& lv, u
 #pragma unroll
 		for (uint32_t k = 0; k < NG; ++k) {
 			asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(grp[k][0]), "+v"(grp[k][1]), "+v"(grp[k][2]), "+v"(grp[k][3]) : [n] "n"(4 * (NG - 1 - k)) : "memory");
-			if (round < count) add_half(round + threadIdx.x + 4u * k * THREADS, grp[k]);
+			if (round < count) add_half(std::false_type{}, round + threadIdx.x + 4u * k * THREADS, grp[k]);
 		}
 #endif
 		scan_overflow<F, THREADS>(own, over, overflow, level, bucket, chunk, add);
@@ -214,15 +255,29 @@ TCNN_DEVICE void bucket_level_packed(const GridMeta& meta, const Level<D>& lv, u
 		float bound[F];
 #pragma unroll
 		for (uint32_t f = 0; f < F; ++f) bound[f] = 0.0f;
+		constexpr float BOUND_UNITS = HALF_IS_BF16 ? 1.0f : 16777216.0f;  // what `bound` counts in: gradient units, or 2^-24 of them (IEEE half, below)
 		auto add_packed = [&](uint32_t index, const uint32_t* payload) {
 			const uint32_t rel = index & (entries_per_bucket - 1u);
 #pragma unroll
 			for (uint32_t p = 0; p < PW; ++p) {
-				const h2 v = bits_h2(payload[p]);
-				const float f0 = (float)v[0], f1 = (float)v[1];
-				bound[2 * p] += __builtin_fabsf(f0);
-				bound[2 * p + 1] += __builtin_fabsf(f1);
-				const int v0 = to_fixed32(f0, sc), v1 = to_fixed32(f1, sc);
+				int v0, v1;
+				if constexpr (HALF_IS_BF16) {
+					const h2 v = bits_h2(payload[p]);
+					const float f0 = (float)v[0], f1 = (float)v[1];
+					bound[2 * p] += __builtin_fabsf(f0);
+					bound[2 * p + 1] += __builtin_fabsf(f1);
+					v0 = to_fixed32(f0, sc);
+					v1 = to_fixed32(f1, sc);
+				} else {
+					// IEEE half: the bound is kept in the table's own units, sum |v * 2^24| -- the same sum times a power of two, rounded in the
+					// same places -- so that one scaled value serves the bound and the conversion (BOUND_UNITS at the test below)
+					float s0, s1;
+					half_pair_times_2_24(payload[p], s0, s1);
+					add_abs(bound[2 * p], s0);
+					add_abs(bound[2 * p + 1], s1);
+					v0 = fixed32_of_scaled(s0);
+					v1 = fixed32_of_scaled(s1);
+				}
 				const unsigned long long x = ((unsigned long long)(uint32_t)(v1 + (v0 >> 31)) << 32) | (unsigned long long)(uint32_t)v0;
 				if (!(diag_owner & 2u) || x == 0x123456789ull) lds_atomic_add_u64(&tab[rel * PW + p], x);
 			}
@@ -241,7 +296,7 @@ TCNN_DEVICE void bucket_level_packed(const GridMeta& meta, const Level<D>& lv, u
 			float total = 0.0f;
 #pragma unroll
 			for (uint32_t w = 0; w < N_WAVES; ++w) total += bound_parts[w][f];
-			safe = safe && total < sc.safe_abs_sum();
+			safe = safe && total < sc.safe_abs_sum() * BOUND_UNITS;
 		}
 		if (safe && !(diag_owner & 4u)) {
 			auto unpack = [&](uint32_t e2) {

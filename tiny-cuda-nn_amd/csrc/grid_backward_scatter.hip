@@ -52,6 +52,7 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 	const bool per_sample = io.max_level != nullptr;
 	if (!per_sample && level_is_off<false>(meta, level, F)) return;  // no records, the owners store zeros
 	const Level<D> lv = make_level<D>(meta, level);
+	const bool linear = !lv.smooth && !lv.nearest;
 	// Zero records.  Under the loss scale the products (GRAD_T)weight * dL/dy underflow to +-0 in 16 bits for much of a converged fit.  The owners
 	// sum in exact fixed point and store +0 for an entry nothing was added to, so a record of zeros changes no bit of the gradient: a pair whose
 	// two payloads are all +-0 is not ranked, staged or queued, and a zero record that would travel through the overflow list is not pushed.
@@ -147,15 +148,18 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 		}
 		// ---- derive the records of my samples; rank each pair within its bucket
 		uint32_t ridx[SPT][N_CORNERS], rank[SPT][N_PAIRS_PER_SAMPLE], pay[SPT][N_CORNERS][PW];
-		auto derive = [&](auto fast_tag) {
-			constexpr bool FAST = decltype(fast_tag)::value;
+		// FAST, LINEAR: the table's kind and the interpolation are properties of the level, decided once ahead of the records (below).  As
+		// run-time values the interpolation costs every sample the Smoothstep polynomial of each dimension and a select per weight.
+		auto derive = [&](auto fast_arg, auto linear_arg) {
+			constexpr bool FAST = decltype(fast_arg)::value, LINEAR = decltype(linear_arg)::value;
+			const bool nearest = LINEAR ? false : lv.nearest;
 #pragma unroll
 			for (uint32_t s = 0; s < SPT; ++s) {
 				bool valid = tile * TILE + s * BUCKET_THREADS + threadIdx.x < io.n && !((off_mask >> s) & 1u);
 				if constexpr (second_order) {
 					if (per_sample && level_is_off<false>(meta, io, min(tile * TILE + s * BUCKET_THREADS + threadIdx.x, io.n - 1u), level, F)) valid = false;
 				}
-				const Cell<D> c = make_cell<D, FAST>(lv, x[s]);
+				const Cell<D> c = make_cell<D, FAST, LINEAR>(lv, x[s]);
 				float dd[D];
 #pragma unroll
 				for (uint32_t d = 0; d < D; ++d) dd[d] = 0.0f;
@@ -165,7 +169,7 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 				for (uint32_t idx = 0; idx < N_CORNERS; ++idx) {
 					float weight;
 					if constexpr (second_order) weight = corner_weight_second_order<D>(lv, c, idx, dd);
-					else weight = lv.nearest ? 1.0f : corner_weight<D>(c, idx);
+					else weight = nearest ? 1.0f : corner_weight<D>(c, idx);
 					if constexpr (second_order && HALF_IS_BF16) weight_abs_sum += __builtin_fabsf(weight);
 					if constexpr (F == 1) {
 						pay[s][idx][0] = __builtin_bit_cast(uint32_t, weight * (float)g[s][0]);
@@ -203,14 +207,14 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 					}
 					const bool nz0 = keep_zero || (mag0 & PAYLOAD_MAGNITUDE) != 0u, nz1 = keep_zero || (mag1 & PAYLOAD_MAGNITUDE) != 0u;
 					if constexpr (EXP_COUNT_ZERO_PAIRS) {  // (false in the product build, exp_diag.h: the pairs of the level, and the all-zero ones among them)
-						if (valid && (pr == 0u || !lv.nearest)) exp_count_pair(level, ((mag0 | (lv.nearest ? 0u : mag1)) & PAYLOAD_MAGNITUDE) == 0u);
+						if (valid && (pr == 0u || !nearest)) exp_count_pair(level, ((mag0 | (nearest ? 0u : mag1)) & PAYLOAD_MAGNITUDE) == 0u);
 					}
-					const bool live = valid && (pr == 0u || !lv.nearest) && (nz0 || (nz1 && !lv.nearest));
+					const bool live = valid && (pr == 0u || !nearest) && (nz0 || (nz1 && !nearest));
 					const uint32_t bucket = ridx[s][2 * pr] >> shift;
 					if (!live) {
 						ridx[s][2 * pr] = BUCKET_INVALID_INDEX;
 						ridx[s][2 * pr + 1] = BUCKET_INVALID_INDEX;
-					} else if (lv.nearest) {
+					} else if (nearest) {
 						ridx[s][2 * pr + 1] = BUCKET_INVALID_INDEX;
 					} else if constexpr (FAST) {
 						if (!fast_together) {
@@ -234,7 +238,11 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 				}
 			}
 		};
-		if (lv.fast) derive(std::true_type{}); else derive(std::false_type{});
+		if (lv.fast) {
+			if (linear) derive(std::true_type{}, std::true_type{}); else derive(std::true_type{}, std::false_type{});
+		} else {
+			if (linear) derive(std::false_type{}, std::true_type{}); else derive(std::false_type{}, std::false_type{});
+		}
 		// the next tile's inputs travel while this one is ranked, reordered and written
 		const uint32_t next_tile = tile + plan.wgs_per_level;
 		if (next_tile < plan.tiles) load_tile(next_tile, x_next, g_next);
@@ -280,11 +288,16 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_grid_bucket_scatter(const Gr
 				if (word0 == BUCKET_INVALID_INDEX) continue;
 				const uint32_t pos = delta[(word0 & PAIR_INDEX_MASK) >> shift] + rank[s][pr];
 				if (diag_scatter & 4u) continue;
-				stage[pos * PWP] = word0;
+#if defined(TCNN_HOST_EMU)
+				uint32_t* dst = stage + pos * PWP;
+#else
+				uint32_t* dst = stage + __umul24(pos, PWP);  // pos < N_PAIR: one 24-bit multiply (as 32-bit index arithmetic it became a 64-bit multiply-add)
+#endif
+				dst[0] = word0;
 #pragma unroll
 				for (uint32_t p = 0; p < PW; ++p) {
-					stage[pos * PWP + 1 + p] = pay[s][2 * pr][p];
-					stage[pos * PWP + 1 + PW + p] = pay[s][2 * pr + 1][p];
+					dst[1 + p] = pay[s][2 * pr][p];
+					dst[1 + PW + p] = pay[s][2 * pr + 1][p];
 				}
 			}
 		}

@@ -110,18 +110,21 @@ struct Cell {
 };
 
 // reference common_device.h:1016-1043 (pos_fract) for every dimension of one sample (x = its position)
-template <uint32_t D, bool FAST>
+// NOT_SMOOTH: the caller has established that the level does not interpolate with Smoothstep (the record scatter decides it once per
+// workgroup): the run-time form computes both and selects per value
+template <uint32_t D, bool FAST, bool NOT_SMOOTH = false>
 TCNN_DEVICE Cell<D> make_cell(const Level<D>& lv, const float (&x)[D]) {
 	constexpr uint32_t primes[7] = {1u, 2654435761u, 805459861u, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
 	Cell<D> c;
+	const bool smooth = NOT_SMOOTH ? false : lv.smooth;
 #pragma unroll
 	for (uint32_t d = 0; d < D; ++d) {
 		float p = __builtin_fmaf(lv.scale, x[d], 0.5f);
 		const float tmp = __builtin_floorf(p);
 		c.grid[d] = (uint32_t)(int)tmp;
 		p -= tmp;
-		c.derivative[d] = lv.smooth ? smoothstep_derivative(p) : 1.0f;
-		if (lv.smooth) p = smoothstep(p);
+		c.derivative[d] = smooth ? smoothstep_derivative(p) : 1.0f;
+		if (smooth) p = smoothstep(p);
 		c.w[d][0] = 1 - p;
 		c.w[d][1] = p;
 		if constexpr (FAST) {
