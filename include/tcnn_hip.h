@@ -101,6 +101,24 @@ int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream, 
                                         const float* dL_ddLdinput, const float* input, const void* dL_doutput,
                                         void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput, const void* params);
 void tcnn_context_destroy(tcnn_context_t* ctx);
+/* inference / forward / backward with the CALLER'S 16-bit input and input-gradient matrices (no reference counterpart): `input` and
+ * `dL_dinput` are dense [n_elements][n_input_dims] in the library's 16-bit type (fp16; bf16 in libtcnn_hip_bf16.so), everything else is as
+ * in the three entries above.  For a network fed by a 16-bit producer (an encoding module, a slice or concatenation of its output): no
+ * fp32 copy of the matrix on the way in, none of its gradient on the way out.  Supported by exactly the modules tcnn_create_network makes
+ * (an Identity encoding with scale 1 and offset 0 in front of the network, which is exact on 16-bit values), at every width and output
+ * count those have; tcnn_module_supports_half_input says 1 for them.  Every other module: 0, and the three calls return
+ * TCNN_ERROR_UNSUPPORTED with the encoding's name in tcnn_last_error().  Results are bit-equal to the fp32 entries on the widened input
+ * (dL_dinput: to their fp32 result, which holds 16-bit values, narrowed).  A context made by tcnn_module_forward_half_input goes to
+ * tcnn_module_backward_half_input, one made by tcnn_module_forward to tcnn_module_backward; the other pairing is TCNN_ERROR.  `input` of
+ * the backward entry is not read (may be NULL).  No alignment is required of either matrix (16-byte aligned ones move in 16-byte accesses). */
+int tcnn_module_supports_half_input(const tcnn_module_t* m);
+int tcnn_module_inference_half_input(tcnn_module_t* m, tcnn_stream_t stream, uint32_t n_elements, const void* input, void* output,
+                                     void* params);
+int tcnn_module_forward_half_input(tcnn_module_t* m, tcnn_stream_t stream, uint32_t n_elements, const void* input, void* output,
+                                   void* params, int prepare_input_gradients, tcnn_context_t** ctx);
+int tcnn_module_backward_half_input(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_context_t* ctx, uint32_t n_elements,
+                                    void* dL_dinput, const void* dL_doutput, void* dL_dparams, const void* input,
+                                    const void* output, const void* params);
 
 uint32_t tcnn_module_n_input_dims(const tcnn_module_t* m);
 uint32_t tcnn_module_n_output_dims(const tcnn_module_t* m); /* PADDED width, cpp_api.cu:137 */

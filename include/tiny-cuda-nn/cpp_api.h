@@ -145,6 +145,25 @@ public:
 		m_max_level_gpu = value;
 	}
 
+	// Beyond the reference (tcnn_module_*_half_input): the caller's own 16-bit input / dL_dinput matrices, [n_elements][n_input_dims] in the
+	// library's 16-bit type, for the modules create_network makes; every other module throws.  A Context of forward_half_input goes to
+	// backward_half_input, one of forward() to backward().
+	bool supports_half_input() const { return tcnn_module_supports_half_input(m_) != 0; }
+	void inference_half_input(hipStream_t stream, uint32_t n_elements, const void* input, void* output, void* params) {
+		check(tcnn_module_inference_half_input(m_, stream, n_elements, input, output, params));
+	}
+	Context forward_half_input(hipStream_t stream, uint32_t n_elements, const void* input, void* output, void* params, bool prepare_input_gradients) {
+		tcnn_context_t* c = nullptr;
+		check(tcnn_module_forward_half_input(m_, stream, n_elements, input, output, params, prepare_input_gradients, &c));
+		Context result;
+		result.ctx = std::make_unique<HipContext>(c);
+		return result;
+	}
+	void backward_half_input(hipStream_t stream, const Context& ctx, uint32_t n_elements, void* dL_dinput, const void* dL_doutput, void* dL_dparams, const void* input,
+	                         const void* output, const void* params) {
+		check(tcnn_module_backward_half_input(m_, stream, handle_of(ctx), n_elements, dL_dinput, dL_doutput, dL_dparams, input, output, params));
+	}
+
 	tcnn_module_t* c_handle() const { return m_; }
 
 private:

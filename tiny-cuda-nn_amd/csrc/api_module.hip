@@ -110,6 +110,7 @@ int tcnn_module_backward(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_cont
 	(void)output;
 	TCNN_API_BEGIN
 	if (!ctx) throw std::runtime_error("backward: missing forward context");
+	if (ctx->ctx.half_input) throw std::runtime_error("backward: this context was made by tcnn_module_forward_half_input; its backward pass is tcnn_module_backward_half_input");
 	if (m->fp32_io) {  // bare encodings only: neither `output` nor the parameters are needed by their first-order backward pass
 		(void)params;
 		encoding_backward_f32((hipStream_t)stream, m->md, IoLayout::dense(m->md), ctx->ctx, n, dL_dinput, (const float*)dL_doutput, (float*)dL_dparams, input);
@@ -118,6 +119,44 @@ int tcnn_module_backward(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_cont
 	model_backward((hipStream_t)stream, nullptr, m->md, IoLayout::dense(m->md), ctx->ctx, n, dL_dinput, (const half_t*)dL_doutput, (half_t*)dL_dparams, input, (const half_t*)output,
 	               (const half_t*)params,
 	               dL_dparams ? TCNN_GRADIENT_OVERWRITE : TCNN_GRADIENT_IGNORE, m->lds_level_budget);  // cpp_api.cu:115
+	TCNN_API_END
+}
+
+// ---- the same three with the caller's own 16-bit input / dL_dinput matrices ([n][n_input_dims] dense, fp16 -- bf16 in libtcnn_hip_bf16.so), for
+// the modules tcnn_create_network makes (model_exec.h half_input_refusal): no fp32 copy of a matrix that a 16-bit producer wrote and the
+// network reads in 16 bits anyway.  Same bits as the fp32 entries on the widened matrix.
+int tcnn_module_supports_half_input(const tcnn_module_t* m) { return m && !m->fp32_io && half_input_refusal(m->md).empty() ? 1 : 0; }
+
+int tcnn_module_inference_half_input(tcnn_module_t* m, tcnn_stream_t stream, uint32_t n, const void* input, void* output, void* params) {
+	TCNN_API_BEGIN
+	if (!m) throw std::runtime_error("tcnn_module_inference_half_input: null module");
+	if (const int r = refuse_half_input(m->md)) return r;
+	model_forward((hipStream_t)stream, nullptr, m->md, IoLayout::dense(m->md), n, nullptr, (half_t*)output, (const half_t*)params, nullptr, false, nullptr, (const half_t*)input);
+	TCNN_API_END
+}
+
+int tcnn_module_forward_half_input(tcnn_module_t* m, tcnn_stream_t stream, uint32_t n, const void* input, void* output, void* params, int prepare_input_gradients,
+                                   tcnn_context_t** ctx) {
+	TCNN_API_BEGIN
+	if (!m || !ctx) throw std::runtime_error("tcnn_module_forward_half_input: null argument");
+	if (const int r = refuse_half_input(m->md)) return r;
+	auto c = std::make_unique<tcnn_context>();
+	model_forward((hipStream_t)stream, nullptr, m->md, IoLayout::dense(m->md), n, nullptr, (half_t*)output, (const half_t*)params, &c->ctx, prepare_input_gradients != 0, nullptr,
+	              (const half_t*)input);
+	*ctx = c.release();
+	TCNN_API_END
+}
+
+int tcnn_module_backward_half_input(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_context_t* ctx, uint32_t n, void* dL_dinput, const void* dL_doutput, void* dL_dparams,
+                                    const void* input, const void* output, const void* params) {
+	(void)input;  // (the identity's backward pass does not read it)
+	TCNN_API_BEGIN
+	if (!m) throw std::runtime_error("tcnn_module_backward_half_input: null module");
+	if (const int r = refuse_half_input(m->md)) return r;
+	if (!ctx) throw std::runtime_error("backward: missing forward context");
+	if (!ctx->ctx.half_input) throw std::runtime_error("backward_half_input: this context was made by tcnn_module_forward; its backward pass is tcnn_module_backward");
+	model_backward((hipStream_t)stream, nullptr, m->md, IoLayout::dense(m->md), ctx->ctx, n, nullptr, (const half_t*)dL_doutput, (half_t*)dL_dparams, nullptr, (const half_t*)output,
+	               (const half_t*)params, dL_dparams ? TCNN_GRADIENT_OVERWRITE : TCNN_GRADIENT_IGNORE, m->lds_level_budget, (half_t*)dL_dinput);
 	TCNN_API_END
 }
 

@@ -33,6 +33,9 @@ struct ForwardCtx {
 	// run with these, whatever the setters have been told since (EncodingDesc::max_level_gpu says whose memory the array is)
 	float max_level = 1.0f;
 	const float* max_level_gpu = nullptr;
+	// filled by a *_half_input forward pass (the caller's 16-bit matrix stood where the fp32 one stands): the backward pass of this context is
+	// the *_half_input one, and the other way round
+	bool half_input = false;
 	void keep_max_level(const EncodingDesc& e) {
 		max_level = e.grid.max_level;
 		max_level_gpu = e.max_level_gpu;
@@ -60,13 +63,19 @@ void encoding_forward(hipStream_t stream, Profiler* profiler, const Model& md, c
 void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const half_t* dL_denc,
                        uint32_t stride_k, uint32_t stride_i, half_t* dL_dparams, bool want_grads, bool accumulate, const float* input,
                        uint32_t lds_level_budget, const LevelGroups* groups = nullptr);
+// The caller's own 16-bit input / dL_dinput matrices (tcnn_module_*_half_input; dense [n][n_input_dims] in the library's 16-bit type) go to
+// exactly the modules tcnn_create_network makes: a network behind an Identity encoding with scale 1 and offset 0, which is exact on values of
+// that type.  Why `md` is not one of them (empty: it is); refuse_half_input sets that as the last error and returns TCNN_ERROR_UNSUPPORTED.
+std::string half_input_refusal(const Model& md);
+int refuse_half_input(const Model& md);
 // NetworkWithInputEncoding::forward_impl / inference_mixed_precision_impl (:60-81).  ctx == nullptr: inference.
+// input16 (only where half_input_refusal(md) is empty; `input` is then ignored): half_input_pad writes the encoded matrix from it.
 void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, half_t* output, const half_t* params,
-                   ForwardCtx* ctx, bool prepare_input_gradients, const MlpF32Output* f32 = nullptr);
+                   ForwardCtx* ctx, bool prepare_input_gradients, const MlpF32Output* f32 = nullptr, const half_t* input16 = nullptr);
 // NetworkWithInputEncoding::backward_impl (:83-113) / GridEncodingTemplated::backward_impl (grid.h:817-908)
 void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const half_t* dL_doutput,
                     half_t* dL_dparams, const float* input, const half_t* output, const half_t* params, int gradient_mode,
-                    uint32_t lds_level_budget);
+                    uint32_t lds_level_budget, half_t* dL_dinput16 = nullptr);  // dL_dinput16: of a context made with input16, instead of dL_dinput
 // network->inference into the caller's fp32 matrix (object.h:214-271)
 void inference_to_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const half_t* params, float* out, uint32_t stride_i, uint32_t stride_j);
 // Encoding<float>: a bare encoding that computes in fp32 (model_exec.hip)

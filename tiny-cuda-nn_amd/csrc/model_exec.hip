@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "half_input_kernels.h"
 #include "host_common.h"
 #include "switches.h"
 
@@ -15,6 +16,22 @@ int refuse_max_level(const Model& md) {
 	set_last_error(why);
 	return TCNN_ERROR_UNSUPPORTED;
 }
+
+std::string half_input_refusal(const Model& md) {
+	const EncodingDesc& e = md.enc;
+	const std::string prefix = std::string("half_input: ") + e.name();
+	if (!md.has_network) return prefix + " is a bare encoding: 16-bit inputs go to the modules tcnn_create_network makes (positions need fp32)";
+	if (e.kind != EncodingKind::Identity) return prefix + " in front of the network reads fp32 inputs: 16-bit inputs go to the modules tcnn_create_network makes";
+	if (e.id_scale != 1.0f || e.id_offset != 0.0f) return prefix + " with a scale other than 1 or an offset other than 0 is not exact on 16-bit values";
+	return "";
+}
+int refuse_half_input(const Model& md) {
+	const std::string why = half_input_refusal(md);
+	if (why.empty()) return TCNN_OK;
+	set_last_error(why);
+	return TCNN_ERROR_UNSUPPORTED;
+}
+static uint16_t half_bits(float v) { return __builtin_bit_cast(uint16_t, (half_t)v); }
 
 void check_batch(uint32_t n, uint32_t widest) {
 	if (n % BATCH_SIZE_GRANULARITY != 0) {  // object.h:170, 217, 298
@@ -195,8 +212,10 @@ static bool backward_recomputes(const Model& md) { return g_fused_network_passes
 
 // NetworkWithInputEncoding::forward_impl / inference_mixed_precision_impl (:60-81).  ctx == nullptr: inference.
 void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, half_t* output, const half_t* params,
-                          ForwardCtx* ctx, bool prepare_input_gradients, const MlpF32Output* f32) {
+                          ForwardCtx* ctx, bool prepare_input_gradients, const MlpF32Output* f32, const half_t* input16) {
 	check_batch(n, widest_matrix(md));
+	if (input16 && !half_input_refusal(md).empty()) throw std::runtime_error(half_input_refusal(md));
+	if (ctx) ctx->half_input = input16 != nullptr;
 	if (n == 0) return;
 	if (ctx) {
 		ctx->stream = stream;
@@ -215,7 +234,7 @@ void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, cons
 	// inference into the caller's fp32 matrix with an Identity encoding that pads nothing: the inference kernel reads the fp32 input itself
 	// (MlpF32Input; no encoding kernel, no encoded matrix)
 	const EncodingDesc& e = md.enc;
-	if (!ctx && e.kind == EncodingKind::Identity && e.n_dims == e.padded_output_width && layout.in_stride_i == e.n_dims && layout.in_stride_d == 1u &&
+	if (!ctx && !input16 && e.kind == EncodingKind::Identity && e.n_dims == e.padded_output_width && layout.in_stride_i == e.n_dims && layout.in_stride_d == 1u &&
 	    ((uintptr_t)input & 15u) == 0u && g_fused_identity_input.load() != 0 && mlp_infer_f32_input_supported(md.net.mlp, n)) {
 		MlpF32Input f32_input;
 		f32_input.x = input;
@@ -229,7 +248,12 @@ void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, cons
 	Scratch enc_local;
 	Scratch& enc = ctx ? ctx->enc : enc_local;
 	enc = Scratch(stream, (size_t)md.enc.padded_output_width * n * sizeof(half_t));
-	encoding_forward(stream, profiler, md, layout, n, input, params + md.n_mlp_params(), enc.as<half_t>(), /*soa=*/true, dy_dx, ctx, prepare_input_gradients);
+	if (input16) {  // the Identity encoding's bits (scale 1, offset 0, padding 1) without the fp32 matrix in between
+		ProfScope prof_enc(profiler, stream, STAGE_GRID_FWD);
+		half_input_pad(stream, n, e.n_dims, e.padded_output_width, (const uint16_t*)input16, (uint16_t*)enc.ptr, half_bits(1.0f));
+	} else {
+		encoding_forward(stream, profiler, md, layout, n, input, params + md.n_mlp_params(), enc.as<half_t>(), /*soa=*/true, dy_dx, ctx, prepare_input_gradients);
+	}
 	half_t* hidden = nullptr;
 	if (ctx && !backward_recomputes(md)) {
 		ctx->hidden = Scratch(stream, mlp_saved_activation_bytes(md.net.mlp, n));
@@ -272,10 +296,11 @@ uint32_t widest_matrix(const Model& md) {
 // NetworkWithInputEncoding::backward_impl (:83-113) / GridEncodingTemplated::backward_impl (grid.h:817-908)
 void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const half_t* dL_doutput,
                            half_t* dL_dparams, const float* input, const half_t* output, const half_t* params, int gradient_mode,
-                           uint32_t lds_level_budget) {
+                           uint32_t lds_level_budget, half_t* dL_dinput16) {
 	check_batch(n, widest_matrix(md));
 	if (n == 0) return;
 	if (ctx.n != n) throw std::runtime_error("backward: batch size does not match the forward context");
+	if (dL_dinput16 && (dL_dinput || !ctx.half_input)) throw std::runtime_error("backward: a 16-bit dL_dinput belongs to a context made with a 16-bit input");
 	const bool recompute = md.has_network && !ctx.hidden.ptr;  // the context holds the encoded input only (see g_fused_network_passes)
 	if (recompute && (!ctx.enc.ptr || !mlp_train_supported(md.net.mlp))) {
 		throw std::runtime_error("backward: this context holds no saved activations and the network has no single-kernel backward pass");
@@ -283,13 +308,21 @@ void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, con
 	const bool want_grads = gradient_mode != TCNN_GRADIENT_IGNORE && dL_dparams != nullptr;
 	const bool accumulate = gradient_mode == TCNN_GRADIENT_ACCUMULATE;
 	const EncodingDesc& e = md.enc;
-	if (!want_grads && !dL_dinput) return;
+	if (!want_grads && !dL_dinput && !dL_dinput16) return;
+	// the encoding's share of the pass, from the feature-major dL/d(encoded input) the network kernels wrote
+	auto encoding_share = [&](const half_t* dL_denc, uint32_t stride_k, uint32_t stride_i) {
+		if (ctx.half_input) {  // identity.h:83 with scale 1, without the fp32 matrix in between: the first n_dims rows as they are
+			if (dL_dinput16) half_input_unpad(stream, n, e.n_dims, (const uint16_t*)dL_denc, (uint16_t*)dL_dinput16);
+			return;
+		}
+		encoding_backward(stream, profiler, md, layout, ctx, n, dL_dinput, dL_denc, stride_k, stride_i, dL_dparams, want_grads, accumulate, input, lds_level_budget);
+	};
 
 	const half_t* dL_denc = dL_doutput;  // bare encoding: gradient of the encoding output, sample-major
 	uint32_t stride_k = 1u, stride_i = e.padded_output_width;
 	Scratch denc;
 	if (md.has_network) {
-		const bool need_denc = (want_grads && e.n_params > 0) || dL_dinput;
+		const bool need_denc = (want_grads && e.n_params > 0) || dL_dinput || dL_dinput16;
 		ProfScope prof(profiler, stream, STAGE_MLP_BWD);
 		Scratch params_t(stream, md.n_mlp_params() * sizeof(half_t));
 		mlp_transpose_weights(stream, md.net.mlp, params, params_t.as<half_t>());
@@ -307,7 +340,7 @@ void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, con
 			dL_denc = denc.as<half_t>();
 			stride_k = n;
 			stride_i = 1u;
-			encoding_backward(stream, profiler, md, layout, ctx, n, dL_dinput, dL_denc, stride_k, stride_i, dL_dparams, want_grads, accumulate, input, lds_level_budget);
+			encoding_share(dL_denc, stride_k, stride_i);
 			return;
 		}
 		Scratch dpre;  // output activation: continue from dL/d(pre-activation) (fully_fused_mlp.cu:760-763)
@@ -328,7 +361,7 @@ void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, con
 		stride_i = 1u;
 	}
 
-	encoding_backward(stream, profiler, md, layout, ctx, n, dL_dinput, dL_denc, stride_k, stride_i, dL_dparams, want_grads, accumulate, input, lds_level_budget);
+	encoding_share(dL_denc, stride_k, stride_i);
 }
 
 // the encoding's share of the backward pass: dL_denc has element (feature k, sample i) at [k * stride_k + i * stride_i]

@@ -112,6 +112,10 @@ _sig("tcnn_module_forward", _i, _vp, _vp, _u32, _vp, _vp, _vp, _i, C.POINTER(_vp
 _sig("tcnn_module_backward", _i, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp)
 _sig("tcnn_module_backward_backward_input", _i, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 _sig("tcnn_context_destroy", None, _vp)
+_sig("tcnn_module_supports_half_input", _i, _vp)
+_sig("tcnn_module_inference_half_input", _i, _vp, _vp, _u32, _vp, _vp, _vp)
+_sig("tcnn_module_forward_half_input", _i, _vp, _vp, _u32, _vp, _vp, _vp, _i, C.POINTER(_vp))
+_sig("tcnn_module_backward_half_input", _i, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp)
 _sig("tcnn_module_n_input_dims", _u32, _vp)
 _sig("tcnn_module_n_output_dims", _u32, _vp)
 _sig("tcnn_module_n_params", _sz, _vp)
@@ -442,10 +446,18 @@ class Module:
     def _torch_output_dtype(self):
         return self._fixed("_output_dtype", lambda: TORCH_DTYPE[Precision(self.output_precision())])
 
+    def supports_half_input(self):
+        """True for the modules create_network makes: fwd / bwd then also take an input in the module's 16-bit type (tcnn_module_*_half_input)."""
+        return self._fixed("_supports_half_input", lambda: bool(_lib.tcnn_module_supports_half_input(self._h)))
+
+    def _takes_half(self, input):
+        return input.dtype != torch.float32 and input.dtype == self._torch_param_dtype() and self.supports_half_input()
+
     def fwd(self, input, params):
         _check_input(input)
         _check_input(params)
-        if input.dtype != torch.float32:
+        half = self._takes_half(input)  # the caller's 16-bit matrix as it is: no fp32 copy
+        if input.dtype != torch.float32 and not half:
             raise RuntimeError("input must be float32")
         if params.dtype != self._torch_param_dtype():
             raise RuntimeError("params have the wrong precision")
@@ -456,12 +468,13 @@ class Module:
         with _DeviceGuard(input.device):
             batch_size = input.shape[0]
             output = torch.empty((batch_size, self.n_output_dims()), dtype=self._torch_output_dtype(), device=input.device)
+            inference, forward = (_lib.tcnn_module_inference_half_input, _lib.tcnn_module_forward_half_input) if half else \
+                (_lib.tcnn_module_inference, _lib.tcnn_module_forward)
             if not input.requires_grad and not params.requires_grad:
-                _check(_lib.tcnn_module_inference(self._h, _stream(), batch_size, _ptr(input), _ptr(output), _ptr(params)))
+                _check(inference(self._h, _stream(), batch_size, _ptr(input), _ptr(output), _ptr(params)))
                 return Context(None), output
             h = C.c_void_p()
-            _check(_lib.tcnn_module_forward(self._h, _stream(), batch_size, _ptr(input), _ptr(output), _ptr(params),
-                                            int(input.requires_grad), C.byref(h)))
+            _check(forward(self._h, _stream(), batch_size, _ptr(input), _ptr(output), _ptr(params), int(input.requires_grad), C.byref(h)))
             return Context(h), output
 
     def bwd(self, ctx, input, params, output, dL_doutput):
@@ -469,7 +482,8 @@ class Module:
             raise RuntimeError("Module::bwd: called with invalid context. fwd likely (mistakenly) ran in inference mode.")
         for t in (input, params, output, dL_doutput):
             _check_input(t)
-        if input.dtype != torch.float32 or params.dtype != self._torch_param_dtype() or \
+        half = self._takes_half(input)  # (as fwd decided: the context is one of tcnn_module_forward_half_input) -> a 16-bit dL_dinput
+        if (input.dtype != torch.float32 and not half) or params.dtype != self._torch_param_dtype() or \
                 output.dtype != self._torch_output_dtype() or dL_doutput.dtype != self._torch_output_dtype():
             raise RuntimeError("bwd: wrong tensor precision")
         if input.shape[1] != self.n_input_dims() or output.shape[1] != self.n_output_dims() or \
@@ -477,11 +491,12 @@ class Module:
             raise RuntimeError("bwd: wrong tensor size")
         with _DeviceGuard(input.device):
             batch_size = input.shape[0]
-            dL_dinput = torch.empty((batch_size, input.shape[1]), dtype=torch.float32, device=input.device) if input.requires_grad else None
+            dL_dinput = torch.empty((batch_size, input.shape[1]), dtype=input.dtype, device=input.device) if input.requires_grad else None
             dL_dparams = torch.empty((self.n_params(),), dtype=self._torch_param_dtype(), device=input.device) if params.requires_grad else None
             if input.requires_grad or params.requires_grad:
-                _check(_lib.tcnn_module_backward(self._h, _stream(), ctx._h, batch_size, _ptr(dL_dinput), _ptr(dL_doutput),
-                                                 _ptr(dL_dparams), _ptr(input), _ptr(output), _ptr(params)))
+                backward = _lib.tcnn_module_backward_half_input if half else _lib.tcnn_module_backward
+                _check(backward(self._h, _stream(), ctx._h, batch_size, _ptr(dL_dinput), _ptr(dL_doutput),
+                                _ptr(dL_dparams), _ptr(input), _ptr(output), _ptr(params)))
             return dL_dinput, dL_dparams
 
     def bwd_bwd_input(self, ctx, input, params, dL_ddLdinput, dL_doutput):  # bindings.cpp:193-241
@@ -627,7 +642,7 @@ class ExtModule:
     def __init__(self, m):
         self._m = m
         self._h = C.c_void_p(m.handle())
-        for name in ("fwd", "bwd", "bwd_bwd_input", "initial_params", "n_input_dims", "n_params", "n_output_dims", "name", "max_level", "set_max_level", "set_max_level_gpu"):
+        for name in ("fwd", "bwd", "bwd_bwd_input", "initial_params", "n_input_dims", "n_params", "n_output_dims", "name", "max_level", "set_max_level", "set_max_level_gpu", "supports_half_input"):
             setattr(self, name, getattr(m, name))
         self._param_precision = Precision(m.param_precision())
         self._output_precision = Precision(m.output_precision())

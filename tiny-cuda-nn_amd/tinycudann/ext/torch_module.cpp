@@ -32,6 +32,11 @@ struct Abi {  // include/tcnn_hip.h, the entries this binding calls
 	int (*backward_backward_input)(tcnn_module*, void*, const tcnn_context*, uint32_t, const float*, const float*, const void*, void*, void*, float*,
 	                               const void*) = nullptr;
 	void (*context_destroy)(tcnn_context*) = nullptr;
+	// the same three with the caller's 16-bit input / dL_dinput (modules made by create_network)
+	int (*supports_half_input)(const tcnn_module*) = nullptr;
+	int (*inference_half_input)(tcnn_module*, void*, uint32_t, const void*, void*, void*) = nullptr;
+	int (*forward_half_input)(tcnn_module*, void*, uint32_t, const void*, void*, void*, int, tcnn_context**) = nullptr;
+	int (*backward_half_input)(tcnn_module*, void*, const tcnn_context*, uint32_t, void*, const void*, void*, const void*, const void*, const void*) = nullptr;
 	uint32_t (*n_input_dims)(const tcnn_module*) = nullptr;
 	uint32_t (*n_output_dims)(const tcnn_module*) = nullptr;
 	size_t (*n_params)(const tcnn_module*) = nullptr;
@@ -72,6 +77,10 @@ void bind_library(const std::string& path) {
 	resolve(lib, capi.backward, "tcnn_module_backward");
 	resolve(lib, capi.backward_backward_input, "tcnn_module_backward_backward_input");
 	resolve(lib, capi.context_destroy, "tcnn_context_destroy");
+	resolve(lib, capi.supports_half_input, "tcnn_module_supports_half_input");
+	resolve(lib, capi.inference_half_input, "tcnn_module_inference_half_input");
+	resolve(lib, capi.forward_half_input, "tcnn_module_forward_half_input");
+	resolve(lib, capi.backward_half_input, "tcnn_module_backward_half_input");
 	resolve(lib, capi.n_input_dims, "tcnn_module_n_input_dims");
 	resolve(lib, capi.n_output_dims, "tcnn_module_n_output_dims");
 	resolve(lib, capi.n_params, "tcnn_module_n_params");
@@ -135,6 +144,7 @@ public:
 		n_params_ = capi.n_params(m_);
 		param_precision_ = capi.param_precision(m_);
 		output_precision_ = capi.output_precision(m_);
+		supports_half_input_ = capi.supports_half_input(m_) != 0;
 	}
 	Module(const Module&) = delete;
 	Module& operator=(const Module&) = delete;
@@ -146,7 +156,8 @@ public:
 	std::pair<std::shared_ptr<Context>, torch::Tensor> fwd(torch::Tensor input, torch::Tensor params) {
 		CHECK_INPUT(input);
 		CHECK_INPUT(params);
-		if (input.scalar_type() != torch::kFloat32) throw std::runtime_error("input must be float32");
+		const bool half = takes_half(input);  // the caller's 16-bit matrix as it is: no fp32 copy
+		if (input.scalar_type() != torch::kFloat32 && !half) throw std::runtime_error("input must be float32");
 		if (params.scalar_type() != torch_type(param_precision_)) throw std::runtime_error("params have the wrong precision");
 		if (input.dim() != 2 || input.size(1) != n_input_dims_ || params.size(0) != (int64_t)n_params_) throw std::runtime_error("input / params have the wrong size");
 		if (input.device() != params.device()) throw std::runtime_error("input and params must be on the same device");
@@ -154,11 +165,13 @@ public:
 		const uint32_t batch_size = (uint32_t)input.size(0);
 		torch::Tensor output = torch::empty({(int64_t)batch_size, (int64_t)n_output_dims_}, torch::TensorOptions().dtype(torch_type(output_precision_)).device(input.device()));
 		if (!input.requires_grad() && !params.requires_grad()) {
-			check(capi.inference(m_, current_stream(), batch_size, input.data_ptr<float>(), output.data_ptr(), params.data_ptr()));
+			if (half) check(capi.inference_half_input(m_, current_stream(), batch_size, input.data_ptr(), output.data_ptr(), params.data_ptr()));
+			else check(capi.inference(m_, current_stream(), batch_size, input.data_ptr<float>(), output.data_ptr(), params.data_ptr()));
 			return {std::make_shared<Context>(), output};
 		}
 		tcnn_context* h = nullptr;
-		check(capi.forward(m_, current_stream(), batch_size, input.data_ptr<float>(), output.data_ptr(), params.data_ptr(), input.requires_grad() ? 1 : 0, &h));
+		if (half) check(capi.forward_half_input(m_, current_stream(), batch_size, input.data_ptr(), output.data_ptr(), params.data_ptr(), input.requires_grad() ? 1 : 0, &h));
+		else check(capi.forward(m_, current_stream(), batch_size, input.data_ptr<float>(), output.data_ptr(), params.data_ptr(), input.requires_grad() ? 1 : 0, &h));
 		return {std::make_shared<Context>(h), output};
 	}
 
@@ -170,7 +183,8 @@ public:
 		CHECK_INPUT(params);
 		CHECK_INPUT(output);
 		CHECK_INPUT(dL_doutput);
-		if (input.scalar_type() != torch::kFloat32 || params.scalar_type() != torch_type(param_precision_) || output.scalar_type() != torch_type(output_precision_) ||
+		const bool half = takes_half(input);  // (as fwd decided: the context is one of forward_half_input) -> a 16-bit dL_dinput
+		if ((input.scalar_type() != torch::kFloat32 && !half) || params.scalar_type() != torch_type(param_precision_) || output.scalar_type() != torch_type(output_precision_) ||
 		    dL_doutput.scalar_type() != torch_type(output_precision_)) {
 			throw std::runtime_error("bwd: wrong tensor precision");
 		}
@@ -181,9 +195,12 @@ public:
 		const c10::hip::HIPGuardMasqueradingAsCUDA guard(input.device());
 		const uint32_t batch_size = (uint32_t)input.size(0);
 		c10::optional<torch::Tensor> dL_dinput, dL_dparams;
-		if (input.requires_grad()) dL_dinput = torch::empty({(int64_t)batch_size, input.size(1)}, torch::TensorOptions().dtype(torch::kFloat32).device(input.device()));
+		if (input.requires_grad()) dL_dinput = torch::empty({(int64_t)batch_size, input.size(1)}, torch::TensorOptions().dtype(input.scalar_type()).device(input.device()));
 		if (params.requires_grad()) dL_dparams = torch::empty({(int64_t)n_params_}, torch::TensorOptions().dtype(torch_type(param_precision_)).device(input.device()));
-		if (input.requires_grad() || params.requires_grad()) {
+		if (half && (input.requires_grad() || params.requires_grad())) {
+			check(capi.backward_half_input(m_, current_stream(), ctx->h, batch_size, dL_dinput ? dL_dinput->data_ptr() : nullptr, dL_doutput.data_ptr(),
+			                              dL_dparams ? dL_dparams->data_ptr() : nullptr, input.data_ptr(), output.data_ptr(), params.data_ptr()));
+		} else if (input.requires_grad() || params.requires_grad()) {
 			check(capi.backward(m_, current_stream(), ctx->h, batch_size, dL_dinput ? dL_dinput->data_ptr<float>() : nullptr, dL_doutput.data_ptr(),
 			                   dL_dparams ? dL_dparams->data_ptr() : nullptr, input.data_ptr<float>(), output.data_ptr(), params.data_ptr()));
 		}
@@ -231,6 +248,8 @@ public:
 	int param_precision() const { return param_precision_; }
 	uint32_t n_output_dims() const { return n_output_dims_; }
 	int output_precision() const { return output_precision_; }
+	// modules made by create_network: fwd / bwd also take an input in the module's 16-bit type (tcnn_module_*_half_input)
+	bool supports_half_input() const { return supports_half_input_; }
 	std::string hyperparams_json() const { return capi.hyperparams_json(m_); }
 	std::string name() const { return capi.name(m_); }
 	bool jit_fusion() const { return capi.jit_fusion(m_) != 0; }
@@ -256,10 +275,14 @@ public:
 	uintptr_t handle() const { return (uintptr_t)m_; }  // for the ctypes helpers of _C.py (grid_indices, level tables)
 
 private:
+	bool takes_half(const torch::Tensor& input) const {
+		return supports_half_input_ && input.scalar_type() != torch::kFloat32 && input.scalar_type() == torch_type(param_precision_);
+	}
 	tcnn_module* m_;
 	uint32_t n_input_dims_, n_output_dims_;
 	size_t n_params_;
 	int param_precision_, output_precision_;
+	bool supports_half_input_ = false;
 };
 
 // ---- the autograd function pair (reference modules.py:132-201): forward -> Module::fwd; backward scales dL/doutput by the loss scale, calls
@@ -298,7 +321,8 @@ struct NativeBackwardFunction : public torch::autograd::Function<NativeBackwardF
 			scaled = scaled_doutput(dy, st->loss_scale, torch_type(st->module->output_precision()));
 		}
 		at::AutoGradMode no_grad(false);
-		auto r = st->module->bwd_bwd_input(st->native_ctx, x, params, ddx.to(torch::kFloat32).contiguous(), scaled);
+		// (a 16-bit x belongs to a bare network, whose second-order pass the library refuses as the reference does: widened so that it gets there)
+		auto r = st->module->bwd_bwd_input(st->native_ctx, x.to(torch::kFloat32), params, ddx.to(torch::kFloat32).contiguous(), scaled);
 		// d_dy depends on ddx only; the other two carry one factor of the loss scale through the scaled dL/doutput
 		torch::Tensor d_dy = std::get<0>(r) ? *std::get<0>(r) : torch::Tensor();
 		torch::Tensor d_params = std::get<1>(r) ? *std::get<1>(r) / st->loss_scale : torch::Tensor();
@@ -380,6 +404,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 		.def("param_precision", &Module::param_precision)
 		.def("n_output_dims", &Module::n_output_dims)
 		.def("output_precision", &Module::output_precision)
+		.def("supports_half_input", &Module::supports_half_input)
 		.def("hyperparams_json", &Module::hyperparams_json)
 		.def("name", &Module::name)
 		.def("handle", &Module::handle)

@@ -10,6 +10,8 @@ Behavioural contract kept from the reference:
   * output gradients are multiplied by the loss scale (128 for fp16) before the native backward and
     the returned gradients divided by it (modules.py:161-171);
   * native objects are not pickled; they are rebuilt from the stored configs on unpickling.
+Beyond the reference: a `Network` given an input in its own 16-bit dtype (another module's output) reads it as it is and returns a 16-bit
+input gradient; every other input is cast to fp32 as in the reference.
 Second-order gradients of the grid encoding (`bwd_bwd_input`) are available through double backward, as in the reference.
 """
 import gc
@@ -108,7 +110,8 @@ class _NativeBackwardFunction(torch.autograd.Function):
         with torch.enable_grad():  # keeps dy's requires_grad flag (this method runs under no_grad by default)
             scaled_dy = (dy * scale).to(_precision_dtype(fwd_ctx.native_module)).contiguous()
         with torch.no_grad():
-            d_dy, d_params, d_x = fwd_ctx.native_module.bwd_bwd_input(fwd_ctx.native_ctx, x, params, ddx.to(torch.float).contiguous(), scaled_dy)
+            # (a 16-bit x belongs to a bare network, whose second-order pass the library refuses as the reference does: widened so that it gets there)
+            d_dy, d_params, d_x = fwd_ctx.native_module.bwd_bwd_input(fwd_ctx.native_ctx, x.to(torch.float), params, ddx.to(torch.float).contiguous(), scaled_dy)
             # d_dy depends on ddx only; the other two carry one factor of the loss scale through scaled_dy
             d_params = None if d_params is None else d_params / scale
             d_x = None if d_x is None else d_x / scale
@@ -151,7 +154,11 @@ class Module(torch.nn.Module):
         padded = (batch_size + g - 1) // g * g
         if padded != batch_size:
             x = torch.nn.functional.pad(x, [0, 0, 0, padded - batch_size])
-        if x.dtype != torch.float32 or not x.is_contiguous():
+        if x.dtype == self.dtype and x.dtype != torch.float32 and self.native_tcnn_module.supports_half_input():
+            # a bare network fed the 16-bit matrix another module wrote: the library reads it as it is and returns a 16-bit dL/dx
+            # (tcnn_module_*_half_input) -- no fp32 copy in either direction
+            x = x.contiguous()
+        elif x.dtype != torch.float32 or not x.is_contiguous():
             x = x.to(torch.float).contiguous()
         max_level_gpu = self._max_level_gpu
         if max_level_gpu is not None:
