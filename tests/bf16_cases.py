@@ -558,3 +558,32 @@ def test_network_activations(act, out_act):
     assert torch.allclose(g_pair[:nm].float(), g_fused[:nm].float(), rtol=1.6e-2, atol=1e-3 * float(g_fused[:nm].float().abs().max()) * 2.0 ** -7 + 1e-7)
     assert abs(tm.loss(c2) - loss_fused) <= 1e-5 * abs(loss_fused) + 1e-9
     assert torch.isfinite(g_fused.float()).all()
+
+
+import exact_network_cases as E  # noqa: E402
+
+
+@pytest.mark.parametrize("fused_passes", [True, False], ids=["single-kernel", "saved-activations"])
+@pytest.mark.parametrize("case", E.BF16_CASES, ids=[c.name for c in E.BF16_CASES])
+def test_exact_network_forward_backward(case, fused_passes):
+    """tests/test_gpu_exact_network.py's module forward / backward of 64 x 2 and 128 x 4 with bfloat16 as the 16-bit type: inputs on which every
+    fp32 sum is exact in any order (C1 and C2 re-audited for the type by tests/test_exact_network_reference.py), so prediction, dL/dinput
+    and the parameter gradients equal the float64 restatement rounded to bfloat16 in every bit."""
+    C = tcnn()._C
+    data = E.generate(case, E.BF16)
+    res = E.restate(case, data, E.BF16)
+    to_t = lambda v: torch.from_numpy(E.to_bits(v, E.BF16).view(np.int16)).view(BF).cuda()  # noqa: E731
+    m = C.create_network(case.IN, case.OUT, case.network())
+    x = torch.from_numpy(data.x.astype(np.float32)).cuda().requires_grad_(True)
+    p = to_t(data.params).requires_grad_(True)
+    C.set_fused_network_passes(fused_passes)
+    try:
+        ctx, y = m.fwd(x, p)
+        dx, dp = m.bwd(ctx, x, p, y, to_t(data.dy))
+        torch.cuda.synchronize()
+    finally:
+        C.set_fused_network_passes(True)
+    report = [E.mismatch("prediction", h_np(y), E.to_bits(res.out, E.BF16)),
+              E.mismatch("dL/dinput", dx.cpu().numpy().view(np.uint32), res.dinput.astype(np.float32).view(np.uint32)),
+              E.mismatch("parameter gradients", h_np(dp), E.to_bits(res.grads, E.BF16))]
+    assert not any(report), "\n".join(r for r in report if r)
