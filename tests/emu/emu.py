@@ -2,46 +2,58 @@
 
 TEST INFRASTRUCTURE ONLY.  Lets `pytest -m "not gpu"` run the real kernel code (indexing, MFMA fragment
 bookkeeping, LDS tiles, barriers) on a machine without a GPU and compare it with the CPU oracle.
+
+This module is the one builder and the one loader of the emulator's libraries: build(), available(), lib(bf16), lib_keep(bf16).  The
+feature modules next to it (emu_max_level, emu_zero_records, ...) hold numpy front-ends only and call lib().  A new entry point goes into
+the driver part that includes its kernels (emu_driver.h lists the parts) and its front-end here or into such a module.
 """
 import ctypes as C
 import os
 import subprocess
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 _CSRC = os.path.join(_ROOT, "tiny-cuda-nn_amd", "csrc")
-_LIB = os.path.join(_HERE, "libtcnn_emu.so")            # IEEE fp16, as libtcnn_hip.so
-_LIB_BF16 = os.path.join(_HERE, "libtcnn_emu_bf16.so")  # the same sources with -DTCNN_BF16, as libtcnn_hip_bf16.so
 _CLANG = "/opt/rocm/lib/llvm/bin/clang++"
-
-
-def _build_command(path, extra, force):
-    """The compiler command that (re)builds `path`, or None if it is newer than every source."""
-    srcs = [os.path.join(_HERE, f) for f in ("emu_driver.cpp", "hip_emu.h")]
-    srcs += [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".h"))]
-    newest = max(os.path.getmtime(s) for s in srcs)
-    if not force and os.path.exists(path) and os.path.getmtime(path) >= newest:
-        return None
-    # Both libraries define the same functions and the emulator keeps global state (::emu::g, an inline variable).  Everything is
-    # compiled with hidden visibility except the driver's extern "C" entry points, and linked with -Bsymbolic: neither library
-    # exports its state or can bind to the other's, so both can live in one process (ctypes loads them RTLD_LOCAL).
-    return [_CLANG, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-            "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wl,-Bsymbolic",
-            "-Wno-pass-failed",
+# The driver's parts (emu_driver.h says what goes where), heaviest first.  Each is compiled to an object of its own, side by side.
+_PARTS = ("emu_driver_grid.cpp", "emu_driver_mlp.cpp", "emu_driver_misc.cpp", "emu_driver_half_input.cpp")
+# The libraries, one per real build variant: (keep, bf16) -> (file, parts, defines).  IEEE fp16 as libtcnn_hip.so or -DTCNN_BF16 as
+# libtcnn_hip_bf16.so; the "keep" pair is the grid part alone with the test-only switch -DTCNN_TEST_KEEP_ZERO_RECORDS.
+_VARIANTS = {(keep, bf16): (os.path.join(_HERE, "libtcnn_emu%s%s.so" % ("_keep" if keep else "", "_bf16" if bf16 else "")),
+                            _PARTS[:1] if keep else _PARTS,
+                            (["-DTCNN_TEST_KEEP_ZERO_RECORDS"] if keep else []) + (["-DTCNN_BF16"] if bf16 else []))
+             for keep in (False, True) for bf16 in (False, True)}
+# All libraries define the same functions and the emulator keeps global state (::emu::g, an inline variable: one instance per library).
+# Everything is compiled with hidden visibility except the driver's extern "C" entry points, and linked with -Bsymbolic: no library
+# exports its state or can bind to another's, so all can live in one process (ctypes loads them RTLD_LOCAL).
+_COMPILE = [_CLANG, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wno-pass-failed",
             "-DTCNN_MLP_WAVE_BLOCKS=3",  # few workgroups: the persistent strip loop runs uneven shares
-            ] + extra + ["-I" + _HERE, "-I" + _CSRC, os.path.join(_HERE, "emu_driver.cpp"), "-o", path]
+            "-I" + _HERE, "-I" + _CSRC, "-c"]
+_LINK = [_CLANG, "-shared", "-fPIC", "-Wl,-Bsymbolic"]
+_MAX_JOBS = 16
 
 
 def build(force=False):
-    """Builds both emulator libraries (side by side: each is one long translation unit); returns the fp16 one's path."""
-    commands = [c for c in (_build_command(_LIB, [], force), _build_command(_LIB_BF16, ["-DTCNN_BF16"], force)) if c]
-    running = [subprocess.Popen(c) for c in commands]
-    failed = [c for c, p in zip(commands, running) if p.wait() != 0]
-    if failed:
-        raise subprocess.CalledProcessError(1, failed[0])
-    return _LIB
+    """Builds every emulator library that is missing or older than one of its sources (the driver, hip_emu.h, csrc/*.hip, csrc/*.h)."""
+    srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith((".cpp", ".h"))]
+    srcs += [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".h"))]
+    newest = max(os.path.getmtime(s) for s in srcs)
+    stale = [v for v in _VARIANTS.values() if force or not os.path.exists(v[0]) or os.path.getmtime(v[0]) < newest]
+    if not stale:
+        return
+    with tempfile.TemporaryDirectory(dir=_HERE) as tmp:
+        compiles, links = [], []
+        for path, parts, defines in stale:
+            objects = [os.path.join(tmp, "%s.%s.o" % (os.path.basename(path), part)) for part in parts]
+            compiles += [(_PARTS.index(part), _COMPILE + defines + [os.path.join(_HERE, part), "-o", o]) for part, o in zip(parts, objects)]
+            links.append(_LINK + objects + ["-o", path])
+        with ThreadPoolExecutor(min(_MAX_JOBS, os.cpu_count() or 1)) as pool:  # (list(): a failed command raises here)
+            list(pool.map(subprocess.check_call, [c for _, c in sorted(compiles, key=lambda c: c[0])]))
+            list(pool.map(subprocess.check_call, links))
 
 
 def available():
@@ -79,11 +91,23 @@ def set_bf16(on):
     return previous
 
 
-def lib():
-    if _bf16 not in _libs:
+def _load(keep, bf16):
+    key = (bool(keep), bool(bf16))
+    if key not in _libs:
         build()
-        _libs[_bf16] = C.CDLL(_LIB_BF16 if _bf16 else _LIB)
-    return _libs[_bf16]
+        _libs[key] = C.CDLL(_VARIANTS[key][0])
+        assert _libs[key].emuzr_keeps_zero_records() == int(key[0])
+    return _libs[key]
+
+
+def lib(bf16=None):
+    """The library: the bfloat16 build (True), the fp16 one (False), or whichever set_bf16 chose (None)."""
+    return _load(False, _bf16 if bf16 is None else bf16)
+
+
+def lib_keep(bf16):
+    """The grid part built with -DTCNN_TEST_KEEP_ZERO_RECORDS."""
+    return _load(True, bf16)
 
 
 def _p(a):
@@ -107,21 +131,28 @@ class Grid:
                          self._off.ctypes.data, self._scale.ctypes.data, self._res.ctypes.data)
 
 
-def grid_forward(g, params_h, positions, soa=True, out_stride=None, want_dy_dx=False):
+# In the grid functions `max_level` is a float32 array with one entry per sample (GridIO::max_level) or None (g's scalar holds), and
+# `bf16` chooses the library as lib() does.  Outputs are pre-filled with garbage: every element must be written.
+def _ml(max_level, n):
+    if max_level is None:
+        return None
+    max_level = np.ascontiguousarray(max_level, dtype=np.float32)
+    assert max_level.shape == (n,)
+    return max_level
+
+
+def grid_forward(g, params_h, positions, soa=True, out_stride=None, want_dy_dx=False, max_level=None, bf16=None):
+    """-> features, feature-major [L*F][n] (soa) or sample-major [n][out_stride], and dy_dx [L*F][n][D] if asked for.  Without dy_dx the
+    tiled gather runs, with it the reference-form kernel."""
     og = g.og
     positions = np.ascontiguousarray(positions, dtype=np.float32)
     n = positions.shape[0]
     k = og.n_levels * og.n_features_per_level
-    if soa:
-        out = np.zeros((k, n), dtype=np.uint16)
-        stride = n
-    else:
-        stride = out_stride or k
-        out = np.zeros((n, stride), dtype=np.uint16)
-    dy_dx = np.zeros((k, n, og.n_dims), dtype=np.float32) if want_dy_dx else None
-    r = lib().emu_grid_forward(C.byref(g.c), _p(positions), C.c_uint32(n), _p(params_h), _p(out), C.c_int(int(soa)),
-                               C.c_uint32(stride), _p(dy_dx))
-    assert r == 0
+    stride = n if soa else (out_stride or k)
+    out = np.full((k, n) if soa else (n, stride), 0x7E00, dtype=np.uint16)
+    dy_dx = np.full((k, n, og.n_dims), np.nan, dtype=np.float32) if want_dy_dx else None
+    assert lib(bf16).emu_grid_forward(C.byref(g.c), _p(_ml(max_level, n)), _p(positions), C.c_uint32(n), _p(np.ascontiguousarray(params_h, dtype=np.uint16)), _p(out),
+                                      C.c_int(int(soa)), C.c_uint32(stride), _p(dy_dx)) == 0
     return (out, dy_dx) if want_dy_dx else out
 
 
@@ -137,7 +168,7 @@ def grid_forward_plan(g, n, tile_samples=512):
     return int(tiles), [[tuple(int(v) for v in out[x, k]) for k in range(int(n_seg[x]))] for x in range(8)]
 
 
-def grid_forward_f32(g, params, positions, out_stride=None, want_dy_dx=False):
+def grid_forward_f32(g, params, positions, out_stride=None, want_dy_dx=False, max_level=None, bf16=None):
     """k_grid_forward_f32: fp32 parameters -> fp32 features [n][out_stride] (+ dy_dx [k][n][D])."""
     og = g.og
     positions = np.ascontiguousarray(positions, dtype=np.float32)
@@ -145,19 +176,20 @@ def grid_forward_f32(g, params, positions, out_stride=None, want_dy_dx=False):
     n = positions.shape[0]
     k = og.n_levels * og.n_features_per_level
     stride = out_stride or k
-    out = np.zeros((n, stride), dtype=np.float32)
-    dy_dx = np.zeros((k, n, og.n_dims), dtype=np.float32) if want_dy_dx else None
-    assert lib().emu_grid_forward_f32(C.byref(g.c), _p(positions), C.c_uint32(n), _p(params), _p(out), C.c_uint32(stride), _p(dy_dx)) == 0
+    out = np.full((n, stride), np.nan, dtype=np.float32)
+    dy_dx = np.full((k, n, og.n_dims), np.nan, dtype=np.float32) if want_dy_dx else None
+    assert lib(bf16).emu_grid_forward_f32(C.byref(g.c), _p(_ml(max_level, n)), _p(positions), C.c_uint32(n), _p(params), _p(out), C.c_uint32(stride), _p(dy_dx)) == 0
     return (out, dy_dx) if want_dy_dx else out
 
 
-def grid_backward_f32(g, positions, dL_dy, accumulate_into=None):
+def grid_backward_f32(g, positions, dL_dy, accumulate_into=None, max_level=None, bf16=None):
     og = g.og
     positions = np.ascontiguousarray(positions, dtype=np.float32)
     dL_dy = np.ascontiguousarray(dL_dy, dtype=np.float32)
+    n = positions.shape[0]
     grad = np.full(og.n_params, 7.0, dtype=np.float32) if accumulate_into is None else accumulate_into  # overwrite mode must clear what is there
-    assert lib().emu_grid_backward_f32(C.byref(g.c), _p(positions), C.c_uint32(positions.shape[0]), _p(dL_dy), C.c_uint32(dL_dy.shape[1]), _p(grad),
-                                       C.c_int(int(accumulate_into is not None))) == 0
+    assert lib(bf16).emu_grid_backward_f32(C.byref(g.c), _p(_ml(max_level, n)), _p(positions), C.c_uint32(n), _p(dL_dy), C.c_uint32(dL_dy.shape[1]), _p(grad),
+                                           C.c_int(int(accumulate_into is not None))) == 0
     return grad
 
 
@@ -183,36 +215,33 @@ def grid_owner_stats():
     return int(v[0]), int(v[1])
 
 
-def grid_backward(g, positions, dL_dy_h, soa=True, mode=SLICED_F32, lds_budget=0, grad_init=None, owner=OWNER_PACKED):
-    """owner: accumulator form of the bucket owners (grid_kernels.h grid_owner_mode).  grad_init: half bit patterns to accumulate into (GradientMode::Accumulate); None -> Overwrite into a
-    buffer pre-filled with garbage (the kernel must not rely on a zeroed gradient buffer)."""
+def grid_backward(g, positions, dL_dy_h, soa=True, mode=SLICED_F32, lds_budget=0, grad_init=None, owner=OWNER_PACKED, max_level=None, bf16=None):
+    """owner: accumulator form of the bucket owners (grid_kernels.h grid_owner_mode), set for this call.  grad_init: half bit patterns to accumulate into
+    (GradientMode::Accumulate); None -> Overwrite into a buffer pre-filled with garbage (the kernel must not rely on a zeroed gradient buffer)."""
     og = g.og
     positions = np.ascontiguousarray(positions, dtype=np.float32)
     n = positions.shape[0]
     dL_dy_h = np.ascontiguousarray(dL_dy_h, dtype=np.uint16)
     grad_h = np.full(og.n_params, 0x3C00, dtype=np.uint16) if grad_init is None else grad_init.copy()
     stride = dL_dy_h.shape[1] if not soa else n
-    lib().emu_set_grid_owner_mode(C.c_int(int(owner)))
-    r = lib().emu_grid_backward(C.byref(g.c), _p(positions), C.c_uint32(n), _p(dL_dy_h), C.c_int(int(soa)),
-                                C.c_uint32(stride), _p(grad_h), C.c_int(int(grad_init is not None)), C.c_int(mode), C.c_uint32(lds_budget))
-    assert r == 0
+    assert lib(bf16).emu_grid_backward(C.byref(g.c), _p(_ml(max_level, n)), _p(positions), C.c_uint32(n), _p(dL_dy_h), C.c_int(int(soa)), C.c_uint32(stride), _p(grad_h),
+                                       C.c_int(int(grad_init is not None)), C.c_int(mode), C.c_uint32(lds_budget), C.c_int(int(owner))) == 0
     return grad_h
 
 
-def grid_backward_backward(g, positions, ddx, dL_dy_soa_h, params_h, dy_dx_kn):
-    """Second-order pass.  dL_dy / dL_ddLdy feature-major [K][n]; dy_dx in the kernels' [K][n][D] layout.
-    Returns (grad_half, dL_ddLdy, dL_dx)."""
+def grid_backward_backward(g, positions, ddx, dL_dy_soa_h, params_h, dy_dx_kn, want_params=True, want_input=True, max_level=None, bf16=None):
+    """Second-order pass.  dL_dy / dL_ddLdy feature-major [K][n]; dy_dx in the kernels' [K][n][D] layout, or None: no dL_ddLdy.
+    Returns (grad_half, dL_ddLdy, dL_dx), each None where not asked for."""
     og = g.og
     positions = np.ascontiguousarray(positions, dtype=np.float32)
     ddx = np.ascontiguousarray(ddx, dtype=np.float32)
     n = positions.shape[0]
     dy = np.ascontiguousarray(dL_dy_soa_h, dtype=np.uint16)
-    grad = np.full(og.n_params, 0x3C00, dtype=np.uint16)
-    dLddy = np.zeros_like(dy)
-    dx = np.full((n, og.n_dims), 7.0, dtype=np.float32)
-    r = lib().emu_grid_backward_backward(C.byref(g.c), _p(positions), _p(ddx), C.c_uint32(n), _p(dy), _p(np.ascontiguousarray(params_h, dtype=np.uint16)),
-                                         _p(np.ascontiguousarray(dy_dx_kn, dtype=np.float32)), _p(grad), _p(dLddy), _p(dx))
-    assert r == 0
+    grad = np.full(og.n_params, 0x3C00, dtype=np.uint16) if want_params else None
+    dLddy = np.full_like(dy, 0x7E00) if dy_dx_kn is not None else None
+    dx = np.full((n, og.n_dims), 7.0, dtype=np.float32) if want_input else None
+    assert lib(bf16).emu_grid_backward_backward(C.byref(g.c), _p(_ml(max_level, n)), _p(positions), _p(ddx), C.c_uint32(n), _p(dy), _p(np.ascontiguousarray(params_h, dtype=np.uint16)),
+                                                _p(None if dy_dx_kn is None else np.ascontiguousarray(dy_dx_kn, dtype=np.float32)), _p(grad), _p(dLddy), _p(dx)) == 0
     return grad, dLddy, dx
 
 
@@ -382,13 +411,18 @@ def adam_step(oh, n_matrix, loss_scale, current_step, w32, w16, grads_h, m1, m2,
     """steps_are_deficits: False / True (32-bit deficits) or an AdamStepsForm; deficits8: the byte array of the byte form."""
     e = EmuAdam(*[getattr(oh, f[0]) for f in EmuAdam._fields_])
     lib().emu_adam_step(C.byref(e), C.c_uint32(w32.size), C.c_uint32(n_matrix), C.c_float(loss_scale), C.c_uint32(current_step),
-                        _p(w32), _p(w16), _p(grads_h), _p(m1), _p(m2), _p(steps), C.c_int(int(steps_are_deficits)), _p(deficits8))
+                        _p(w32), _p(w16), _p(grads_h), _p(m1), _p(m2), _p(steps), C.c_int(int(steps_are_deficits)), _p(deficits8),
+                        C.c_int(int(_adam_half_follows_master)))
+
+
+_adam_half_follows_master = False
 
 
 def set_adam_half_follows_master(on):
     """AdamCore::half_follows_master of the following adam_step calls: skipped parameters of a partly stepped lane get their 16-bit weight
     from the fp32 master weight instead of reading it back."""
-    lib().emu_set_adam_half_follows_master(C.c_int(int(on)))
+    global _adam_half_follows_master
+    _adam_half_follows_master = bool(on)
 
 
 def adam_convert_steps(steps_done, steps, deficits8, form_from, form_to):

@@ -1,52 +1,15 @@
-"""numpy front-end for the host-emulator build of csrc/composite_kernels.hip (tests/emu/emu_composite_driver.cpp): a library of its own,
-built the way tests/emu/emu.py builds the main one (same compiler, same flags), IEEE fp16 and -DTCNN_BF16.  TEST INFRASTRUCTURE ONLY.
+"""The emulated kernels of csrc/composite_kernels.hip (tests/emu/emu_driver_misc.cpp, emuc_*).  TEST INFRASTRUCTURE ONLY.
 
 Value matrices are numpy [n, rows] (sample-major, as the oracle's); `soa` runs the kernel on the feature-major transpose the network
 reads.  dtype uint16: the 16-bit type's bit patterns; float32: the fp32 encodings' kernels."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import emu
+from emu import _p, available, lib  # noqa: F401
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "tiny-cuda-nn_amd", "csrc")
-_LIBS = {False: os.path.join(_HERE, "libtcnn_emu_composite.so"), True: os.path.join(_HERE, "libtcnn_emu_composite_bf16.so")}
-_SOURCES = [os.path.join(_HERE, "emu_composite_driver.cpp"), os.path.join(_HERE, "hip_emu.h")] + \
-           [os.path.join(_CSRC, f) for f in ("composite_kernels.hip", "composite_kernels.h", "encoding_device.h", "tcnn_device.h")]
 IDENTITY, ONEBLOB, FREQUENCY, TRIANGLE_WAVE = 0, 1, 2, 3  # composite_kernels.h EncodingPartKind
 KINDS = {"Identity": IDENTITY, "OneBlob": ONEBLOB, "Frequency": FREQUENCY, "TriangleWave": TRIANGLE_WAVE}
-_loaded = {}
-
-
-def available():
-    return emu.available()
-
-
-def build(force=False):
-    newest = max(os.path.getmtime(s) for s in _SOURCES)
-    running = []
-    for bf16, path in _LIBS.items():
-        if force or not os.path.exists(path) or os.path.getmtime(path) < newest:
-            cmd = emu._build_command(path, ["-DTCNN_BF16"] if bf16 else [], True)
-            cmd[cmd.index(os.path.join(_HERE, "emu_driver.cpp"))] = _SOURCES[0]
-            running.append((cmd, subprocess.Popen(cmd)))
-    failed = [c for c, p in running if p.wait() != 0]
-    if failed:
-        raise subprocess.CalledProcessError(1, failed[0])
-
-
-def lib(bf16=False):
-    if bf16 not in _loaded:
-        build()
-        _loaded[bf16] = C.CDLL(_LIBS[bf16])
-    return _loaded[bf16]
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _to_kernel(v, soa):

@@ -1,51 +1,12 @@
-"""numpy front-end for the host-emulator build of csrc/optimizer_kernels.hip (tests/emu/emu_optimizers_driver.cpp): a library of its own,
-built the way tests/emu/emu.py builds the main one (same compiler, same flags), IEEE fp16 and -DTCNN_BF16.  TEST INFRASTRUCTURE ONLY.
+"""The emulated kernels of csrc/optimizer_kernels.hip (tests/emu/emu_driver_misc.cpp, emuo_*).  TEST INFRASTRUCTURE ONLY.
 
 `Kernels(bf16)` offers the kernels under the names tests/optimizer_reference.py gives its numpy restatements, so that its optimizer
 classes (the wrappers' host logic) can run on either.  Arrays are updated in place; 16-bit values are uint16."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import emu
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "tiny-cuda-nn_amd", "csrc")
-_LIBS = {False: os.path.join(_HERE, "libtcnn_emu_optimizers.so"), True: os.path.join(_HERE, "libtcnn_emu_optimizers_bf16.so")}
-_SOURCES = [os.path.join(_HERE, "emu_optimizers_driver.cpp"), os.path.join(_HERE, "hip_emu.h")] + \
-           [os.path.join(_CSRC, f) for f in ("optimizer_kernels.hip", "optimizer_kernels.h", "tcnn_device.h")]
-_loaded = {}
-
-
-def available():
-    return emu.available()
-
-
-def build(force=False):
-    newest = max(os.path.getmtime(s) for s in _SOURCES)
-    running = []
-    for bf16, path in _LIBS.items():
-        if force or not os.path.exists(path) or os.path.getmtime(path) < newest:
-            cmd = emu._build_command(path, ["-DTCNN_BF16"] if bf16 else [], True)
-            cmd[cmd.index(os.path.join(_HERE, "emu_driver.cpp"))] = _SOURCES[0]
-            running.append((cmd, subprocess.Popen(cmd)))
-    failed = [c for c, p in running if p.wait() != 0]
-    if failed:
-        raise subprocess.CalledProcessError(1, failed[0])
-
-
-def lib(bf16=False):
-    if bf16 not in _loaded:
-        build()
-        _loaded[bf16] = C.CDLL(_LIBS[bf16])
-    return _loaded[bf16]
-
-
-def _p(a):
-    assert a.flags["C_CONTIGUOUS"]
-    return a.ctypes.data_as(C.c_void_p)
+from emu import _p, available, lib  # noqa: F401
 
 
 def aligned_zeros(n, dtype):
