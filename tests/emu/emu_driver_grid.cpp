@@ -162,13 +162,13 @@ int emu_grid_backward_input(const EmuGrid* e, uint32_t n, const uint16_t* dL_dy,
 
 // GridEncodingTemplated<float>: fp32 parameters / features / gradients (sample-major [n][stride] features and gradients)
 int emu_grid_forward_f32(const EmuGrid* e, const float* max_level, const float* positions, uint32_t n, const float* params, float* out, uint32_t out_stride, float* dy_dx) {
-	return emu_call(__func__, [&] { grid_forward_f32(nullptr, make_meta(e), make_io(e, positions, n, 1u, out_stride, max_level), params, out, dy_dx); });
+	return emu_call(__func__, [&] { grid_forward(nullptr, make_meta(e), make_io(e, positions, n, 1u, out_stride, max_level), params, out, dy_dx); });
 }
 int emu_grid_backward_f32(const EmuGrid* e, const float* max_level, const float* positions, uint32_t n, const float* dL_dy, uint32_t dy_stride, float* grad, int accumulate) {
-	return emu_call(__func__, [&] { grid_backward_f32(nullptr, make_meta(e), make_io(e, positions, n, 1u, dy_stride, max_level), dL_dy, grad, accumulate != 0); });
+	return emu_call(__func__, [&] { grid_backward(nullptr, make_meta(e), make_io(e, positions, n, 1u, dy_stride, max_level), dL_dy, grad, accumulate != 0); });
 }
 int emu_grid_backward_input_f32(const EmuGrid* e, uint32_t n, const float* dL_dy, uint32_t dy_stride, const float* dy_dx, float* dL_dx) {
-	grid_backward_input_f32(nullptr, e->n_dims, e->n_levels * e->n_feat, make_io(e, nullptr, n, 1u, dy_stride, nullptr), dL_dy, dy_dx, dL_dx, e->n_dims, 1);
+	grid_backward_input(nullptr, e->n_dims, e->n_levels * e->n_feat, make_io(e, nullptr, n, 1u, dy_stride, nullptr), dL_dy, dy_dx, dL_dx, e->n_dims, 1);
 	return 0;
 }
 
@@ -182,8 +182,8 @@ int emuso_second_order_f32(const EmuGrid* e, const float* max_level, const float
 		const GridIO io = make_io(e, positions, n, 1u, stride, max_level, ddx);
 		const uint32_t n_features = e->n_levels * e->n_feat;
 		if (dL_ddLdy) grid_backward_backward_dLdoutput(nullptr, e->n_dims, n_features, stride - n_features, io, dy_dx, dL_ddLdy);
-		if (grad) grid_backward_f32(nullptr, meta, io, dL_dy, grad, false);
-		if (dL_dx) grid_backward_backward_input_f32(nullptr, meta, io, dL_dy, params, dL_dx, e->n_dims, 1);
+		if (grad) grid_backward(nullptr, meta, io, dL_dy, grad, false);
+		if (dL_dx) grid_backward_backward_input(nullptr, meta, io, dL_dy, params, dL_dx, e->n_dims, 1);
 	});
 }
 

@@ -14,7 +14,7 @@ struct tcnn_module {
 	std::string name;
 	uint32_t lds_level_budget = 0;  // 0: default LDS slice size of the sliced grid backward
 	// create_encoding(..., Precision::Fp32) (cpp_api.cu:165-174 -> Encoding<float>): parameters, outputs and gradients are fp32 and the
-	// first-order passes COMPUTE in fp32 (encoding_forward_f32 / encoding_backward_f32: the grid's kernel_grid<float> formulation, fp32
+	// first-order passes COMPUTE in fp32 (encoding_forward<float> / encoding_backward<float>: the grid's kernel_grid<float> formulation, fp32
 	// global atomics for its parameter gradients; frequency / one-blob / identity with float values).  So does the second-order pass
 	// (backward_backward_input, grid only): the T = float instances of the reference's three kernels on the caller's own tensors.
 	// tcnn_set_fp32_second_order(1) brings back the 16-bit stand-ins it used to run on (A/B runs, tests): incoming gradients are scaled
@@ -84,7 +84,7 @@ int tcnn_module_inference(tcnn_module_t* m, tcnn_stream_t stream_, uint32_t n, c
 	TCNN_API_BEGIN
 	hipStream_t stream = (hipStream_t)stream_;
 	if (m->fp32_io) {
-		encoding_forward_f32(stream, m->md, IoLayout::dense(m->md), n, input, (const float*)params, (float*)output, nullptr, false);
+		if (begin_pass(stream, m->md, n)) encoding_forward(stream, nullptr, m->md, IoLayout::dense(m->md), n, input, (const float*)params, (float*)output, 1u, m->md.enc.padded_output_width);
 		return TCNN_OK;
 	}
 	model_forward(stream, nullptr, m->md, IoLayout::dense(m->md), n, input, (half_t*)output, (const half_t*)params, nullptr, false);
@@ -97,7 +97,10 @@ int tcnn_module_forward(tcnn_module_t* m, tcnn_stream_t stream_, uint32_t n, con
 	hipStream_t stream = (hipStream_t)stream_;
 	auto c = std::make_unique<tcnn_context>();
 	if (m->fp32_io) {
-		encoding_forward_f32(stream, m->md, IoLayout::dense(m->md), n, input, (const float*)params, (float*)output, &c->ctx, prepare_input_gradients != 0);
+		if (begin_pass(stream, m->md, n, &c->ctx)) {
+			encoding_forward(stream, nullptr, m->md, IoLayout::dense(m->md), n, input, (const float*)params, (float*)output, 1u, m->md.enc.padded_output_width, &c->ctx,
+			                 prepare_input_gradients != 0);
+		}
 	} else {
 		model_forward(stream, nullptr, m->md, IoLayout::dense(m->md), n, input, (half_t*)output, (const half_t*)params, &c->ctx, prepare_input_gradients != 0);
 	}
@@ -113,7 +116,10 @@ int tcnn_module_backward(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_cont
 	if (ctx->ctx.half_input) throw std::runtime_error("backward: this context was made by tcnn_module_forward_half_input; its backward pass is tcnn_module_backward_half_input");
 	if (m->fp32_io) {  // bare encodings only: neither `output` nor the parameters are needed by their first-order backward pass
 		(void)params;
-		encoding_backward_f32((hipStream_t)stream, m->md, IoLayout::dense(m->md), ctx->ctx, n, dL_dinput, (const float*)dL_doutput, (float*)dL_dparams, input);
+		if (begin_backward(m->md, ctx->ctx, n)) {
+			encoding_backward((hipStream_t)stream, nullptr, m->md, IoLayout::dense(m->md), ctx->ctx, n, dL_dinput, (const float*)dL_doutput, 1u, m->md.enc.padded_output_width,
+			                  (float*)dL_dparams, dL_dparams != nullptr, /*accumulate=*/false, input);  // GradientMode::Overwrite, cpp_api.cu:115
+		}
 		return TCNN_OK;
 	}
 	model_backward((hipStream_t)stream, nullptr, m->md, IoLayout::dense(m->md), ctx->ctx, n, dL_dinput, (const half_t*)dL_doutput, (half_t*)dL_dparams, input, (const half_t*)output,
@@ -203,13 +209,13 @@ int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_,
 			dL_ddLdoutput = ddy16.ptr;
 		}
 	}
-	GridIO io = {input, md.n_input_dims, 1u, n, 1u, e.padded_output_width};  // the bare encoding's output is sample-major (cpp_api.cu:94-95)
-	io.max_level = ctx->ctx.max_level_gpu;  // max_level as the forward pass of this context saw it
-	GridMeta grid = e.grid;
-	grid.max_level = ctx->ctx.max_level;
-	io.ddx = dL_ddLdinput;
-	io.ddx_stride_i = md.n_input_dims;
-	io.ddx_stride_d = 1u;
+	// the bare encoding's output is sample-major (cpp_api.cu:94-95); max_level as the forward pass of this context saw it
+	GridSlice slice = grid_slice(e, IoLayout::dense(md), input, n, 1u, e.padded_output_width).max_level(ctx->ctx.max_level, ctx->ctx.max_level_gpu);
+	slice.io.ddx = dL_ddLdinput;
+	slice.io.ddx_stride_i = md.n_input_dims;
+	slice.io.ddx_stride_d = 1u;
+	const GridMeta& grid = slice.grid;
+	const GridIO& io = slice.io;
 	if (fp32_kernels) {  // the caller's fp32 tensors as they are: no stand-ins, no gradient scale, no 16-bit scratch
 		if (dL_ddLdoutput) {  // grid.h:1012-1035
 			if (!ctx->ctx.dy_dx.ptr) throw std::runtime_error("backward_backward_input: the forward pass did not prepare input gradients");
@@ -217,10 +223,10 @@ int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_,
 			                                 (float*)dL_ddLdoutput);
 		}
 		if ((dL_dparams || dL_dinput) && !dL_doutput) throw std::runtime_error("backward_backward_input: dL_doutput is required for parameter / input gradients");
-		if (dL_dparams && e.n_params > 0) grid_backward_f32(stream, grid, io, (const float*)dL_doutput, (float*)dL_dparams, false);  // grid.h:942-975, GradientMode::Overwrite
+		if (dL_dparams && e.n_params > 0) grid_backward(stream, grid, io, (const float*)dL_doutput, (float*)dL_dparams, false);  // grid.h:942-975, GradientMode::Overwrite
 		if (dL_dinput) {  // grid.h:977-1010
 			if (!params) throw std::runtime_error("backward_backward_input: params are required for the input gradient");
-			grid_backward_backward_input_f32(stream, grid, io, (const float*)dL_doutput, (const float*)params, dL_dinput, md.n_input_dims, 1u);
+			grid_backward_backward_input(stream, grid, io, (const float*)dL_doutput, (const float*)params, dL_dinput, md.n_input_dims, 1u);
 		}
 		return TCNN_OK;
 	}
@@ -233,16 +239,7 @@ int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_,
 		if (!dL_doutput) throw std::runtime_error("backward_backward_input: dL_doutput is required for parameter / input gradients");
 	}
 	if (dL_dparams && e.n_params > 0) {  // grid.h:942-975, GradientMode::Overwrite
-		uint32_t budget = m->lds_level_budget ? m->lds_level_budget : g_default_lds_slice_bytes;
-		GridBackwardWorkspace ws = grid_backward_workspace_size(grid, n, GridBackwardMode::Bucketed, budget);
-		Scratch queues;
-		if (ws.scratch_bytes) {
-			queues = Scratch(stream, ws.scratch_bytes);
-			ws.scratch = queues.ptr;
-			ws.scratch_bytes = queues.bytes;
-			ws.counters = ZeroedCounters::get(stream, ws.n_counters);
-		}
-		grid_backward(stream, grid, io, (const half_t*)dL_doutput, (half_t*)dL_dparams, false, GridBackwardMode::Bucketed, budget, ws);
+		grid_backward_with_workspace(stream, slice, (const half_t*)dL_doutput, (half_t*)dL_dparams, false, GridBackwardMode::Bucketed, m->lds_level_budget);
 	}
 	if (dL_dinput) {  // grid.h:977-1010
 		grid_backward_backward_input(stream, grid, io, (const half_t*)dL_doutput, (const half_t*)params, dL_dinput, md.n_input_dims, 1u);

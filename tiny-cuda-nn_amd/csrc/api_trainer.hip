@@ -213,14 +213,11 @@ static int training_step_fused(tcnn_trainable_model_t* tm, hipStream_t stream, c
 	const half_t* params = use_inference_params ? tm->inference_params() : tm->params;
 	Profiler* profiler = tm->profiler.get();
 	const Model& md = tm->md;
-	check_batch(n, widest_matrix(md));
 	auto c = std::make_unique<tcnn_train_context>();
 	c->n = n;
 	c->stream = stream;
 	ForwardCtx& fc = c->model_ctx;
-	fc.stream = stream;
-	fc.n = n;
-	fc.keep_max_level(md.enc);
+	begin_pass(stream, md, n, &fc);
 	const uint32_t padded = md.padded_output_width();
 	const bool want_grads = gradient_mode != TCNN_GRADIENT_IGNORE;
 	const bool accumulate = gradient_mode == TCNN_GRADIENT_ACCUMULATE;
@@ -240,18 +237,13 @@ static int training_step_fused(tcnn_trainable_model_t* tm, hipStream_t stream, c
 		return TCNN_OK;
 	}
 
-	float* dy_dx = nullptr;
-	if (dL_dinput && e.is_grid()) {
-		fc.dy_dx = Scratch(stream, (size_t)e.n_output_dims * n * md.n_input_dims * sizeof(float));
-		dy_dx = fc.dy_dx.as<float>();
-	}
 	fc.enc = Scratch(stream, (size_t)e.padded_output_width * n * sizeof(half_t));
 	// An Identity encoding that pads nothing is `(T)(x * scale + offset)` per element: the register-resident network kernel reads the caller's
 	// fp32 matrix itself (MlpF32Input) and leaves the encoded matrix behind for the context -- no transpose kernel, no second pass over the input
 	const bool plain_identity = e.kind == EncodingKind::Identity && e.n_dims == e.padded_output_width && layout.in_stride_i == e.n_dims && layout.in_stride_d == 1u;
 	const bool input_by_network = plain_identity && !external_dL_dy && g_fused_identity_input.load() != 0 && n <= (1u << 25) &&
 	                              mlp_train_f32_input_supported(md.net.mlp, n, tm->loss);
-	if (!input_by_network) encoding_forward(stream, profiler, md, layout, n, input, params + md.n_mlp_params(), fc.enc.as<half_t>(), /*soa=*/true, dy_dx, &fc, dL_dinput != nullptr);
+	if (!input_by_network) encoding_forward(stream, profiler, md, layout, n, input, params + md.n_mlp_params(), fc.enc.as<half_t>(), n, 1u, &fc, dL_dinput != nullptr);
 
 	const bool need_denc = (want_grads && e.n_params > 0) || dL_dinput;
 	Scratch denc;

@@ -9,14 +9,12 @@
 namespace tcnn_hip {
 
 // encodings/triangle_wave.h:46-108: n_frequencies outputs per input dimension, padding value 1; dL/dinput recomputes the derivative the
-// reference stores.
+// reference stores.  (Every launcher here is instantiated for T = half_t and float in composite_kernels.hip.)
+template <typename T>
 void triangle_wave_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
-                           uint32_t in_stride_j, half_t* out, uint32_t stride_k, uint32_t stride_i);
-void triangle_wave_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
-                           uint32_t in_stride_j, float* out, uint32_t stride_k, uint32_t stride_i);
-void triangle_wave_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const half_t* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                            const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j);
-void triangle_wave_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const float* dL_dy, uint32_t stride_k, uint32_t stride_i,
+                           uint32_t in_stride_j, T* out, uint32_t stride_k, uint32_t stride_i);
+template <typename T>
+void triangle_wave_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const T* dL_dy, uint32_t stride_k, uint32_t stride_i,
                             const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j);
 
 // One nested encoding without parameters: it reads input dims [in_row, in_row + in_width) and writes rows [out_row, out_row + padded_width)
@@ -34,26 +32,22 @@ struct EncodingParts {
 	void add(const EncodingPart& p);  // throws beyond ENCODING_MAX_PARTS
 };
 // all parts in one launch
-void encoding_parts_forward(hipStream_t stream, const EncodingParts& parts, uint32_t n, const float* in, uint32_t in_stride_i, uint32_t in_stride_d, half_t* out,
-                            uint32_t stride_k, uint32_t stride_i);
-void encoding_parts_forward(hipStream_t stream, const EncodingParts& parts, uint32_t n, const float* in, uint32_t in_stride_i, uint32_t in_stride_d, float* out,
+template <typename T>
+void encoding_parts_forward(hipStream_t stream, const EncodingParts& parts, uint32_t n, const float* in, uint32_t in_stride_i, uint32_t in_stride_d, T* out,
                             uint32_t stride_k, uint32_t stride_i);
 // dL_dx of ALL n_input_dims dims in one launch: a dim some part reads gets that part's gradient, every other dim is written as zero
 // (the caller lets nested encodings WITH parameters overwrite theirs afterwards)
-void encoding_parts_backward(hipStream_t stream, const EncodingParts& parts, uint32_t n, uint32_t n_input_dims, const half_t* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                             const float* in, uint32_t in_stride_i, uint32_t in_stride_d, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_d);
-void encoding_parts_backward(hipStream_t stream, const EncodingParts& parts, uint32_t n, uint32_t n_input_dims, const float* dL_dy, uint32_t stride_k, uint32_t stride_i,
+template <typename T>
+void encoding_parts_backward(hipStream_t stream, const EncodingParts& parts, uint32_t n, uint32_t n_input_dims, const T* dL_dy, uint32_t stride_k, uint32_t stride_i,
                              const float* in, uint32_t in_stride_i, uint32_t in_stride_d, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_d);
 
 // composite.h:47-133.  to_reduce / dL_dunreduced: n_to_reduce blocks of `width` rows, element (row r, sample i) at [r * stride_k + i * stride_i];
 // reduced / dL_dreduced: `width` rows with their own strides.  fp32 accumulation in nested order, rounded to T at the store.
-void reduce_forward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const half_t* to_reduce, uint32_t stride_k, uint32_t stride_i,
-                    half_t* reduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i);
-void reduce_forward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const float* to_reduce, uint32_t stride_k, uint32_t stride_i,
-                    float* reduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i);
-void reduce_backward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const half_t* to_reduce, half_t* dL_dunreduced, uint32_t stride_k,
-                     uint32_t stride_i, const half_t* dL_dreduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i);
-void reduce_backward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const float* to_reduce, float* dL_dunreduced, uint32_t stride_k,
-                     uint32_t stride_i, const float* dL_dreduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i);
+template <typename T>
+void reduce_forward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const T* to_reduce, uint32_t stride_k, uint32_t stride_i,
+                    T* reduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i);
+template <typename T>
+void reduce_backward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const T* to_reduce, T* dL_dunreduced, uint32_t stride_k,
+                     uint32_t stride_i, const T* dL_dreduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i);
 
 }  // namespace tcnn_hip

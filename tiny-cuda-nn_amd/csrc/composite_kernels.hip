@@ -46,35 +46,21 @@ __global__ void __launch_bounds__(CK_THREADS) k_triangle_wave_backward(uint32_t 
 	dL_dx[(size_t)i * dx_stride_i + (size_t)d * dx_stride_j] = triangle_wave_dL_dx<VAL_T>(dL_dy + (size_t)d * n_frequencies * stride_k + (size_t)i * stride_i, stride_k, n_frequencies, x0);
 }
 template <typename VAL_T>
-static void triangle_wave_forward_t(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
-                                    uint32_t in_stride_j, VAL_T* out, uint32_t stride_k, uint32_t stride_i) {
+void triangle_wave_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
+                           uint32_t in_stride_j, VAL_T* out, uint32_t stride_k, uint32_t stride_i) {
 	if (n == 0 || padded == 0) return;
 	TCNN_LAUNCH(k_triangle_wave_forward<VAL_T>, dim3(div_round_up(n * padded, CK_THREADS)), dim3(CK_THREADS), 0, stream, n, n_dims, n_frequencies, padded, in, in_stride_i,
 	            in_stride_j, out, stride_k, stride_i);
 }
 template <typename VAL_T>
-static void triangle_wave_backward_t(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const VAL_T* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                                     const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
+void triangle_wave_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const VAL_T* dL_dy, uint32_t stride_k, uint32_t stride_i,
+                            const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
 	if (n == 0 || n_dims == 0) return;
 	TCNN_LAUNCH(k_triangle_wave_backward<VAL_T>, dim3(div_round_up(n * n_dims, CK_THREADS)), dim3(CK_THREADS), 0, stream, n, n_dims, n_frequencies, dL_dy, stride_k, stride_i, in,
 	            in_stride_i, in_stride_j, dL_dx, dx_stride_i, dx_stride_j);
 }
-void triangle_wave_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
-                           uint32_t in_stride_j, half_t* out, uint32_t stride_k, uint32_t stride_i) {
-	triangle_wave_forward_t<half_t>(stream, n, n_dims, n_frequencies, padded, in, in_stride_i, in_stride_j, out, stride_k, stride_i);
-}
-void triangle_wave_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
-                           uint32_t in_stride_j, float* out, uint32_t stride_k, uint32_t stride_i) {
-	triangle_wave_forward_t<float>(stream, n, n_dims, n_frequencies, padded, in, in_stride_i, in_stride_j, out, stride_k, stride_i);
-}
-void triangle_wave_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const half_t* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                            const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
-	triangle_wave_backward_t<half_t>(stream, n, n_dims, n_frequencies, dL_dy, stride_k, stride_i, in, in_stride_i, in_stride_j, dL_dx, dx_stride_i, dx_stride_j);
-}
-void triangle_wave_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const float* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                            const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
-	triangle_wave_backward_t<float>(stream, n, n_dims, n_frequencies, dL_dy, stride_k, stride_i, in, in_stride_i, in_stride_j, dL_dx, dx_stride_i, dx_stride_j);
-}
+TCNN_INSTANTIATE_VALUE_TYPES(triangle_wave_forward)
+TCNN_INSTANTIATE_VALUE_TYPES(triangle_wave_backward)
 
 // ------------------------------------------------------------------------------------------ all parts without parameters in one launch
 void EncodingParts::add(const EncodingPart& p) {
@@ -160,37 +146,23 @@ __global__ void __launch_bounds__(CK_THREADS) k_encoding_parts_backward(const En
 }
 
 template <typename VAL_T>
-static void encoding_parts_forward_t(hipStream_t stream, const EncodingParts& parts, uint32_t n, const float* in, uint32_t in_stride_i, uint32_t in_stride_d, VAL_T* out,
-                                     uint32_t stride_k, uint32_t stride_i) {
+void encoding_parts_forward(hipStream_t stream, const EncodingParts& parts, uint32_t n, const float* in, uint32_t in_stride_i, uint32_t in_stride_d, VAL_T* out,
+                            uint32_t stride_k, uint32_t stride_i) {
 	if (n == 0 || parts.n_rows == 0) return;
 	check_rows("encoding_parts_forward", n, div_round_up(parts.n_rows, PARTS_ROWS));
 	TCNN_LAUNCH(k_encoding_parts_forward<VAL_T>, dim3(n / CK_THREADS, div_round_up(parts.n_rows, PARTS_ROWS)), dim3(CK_THREADS), 0, stream, parts, n, in, in_stride_i, in_stride_d, out,
 	            stride_k, stride_i);
 }
 template <typename VAL_T>
-static void encoding_parts_backward_t(hipStream_t stream, const EncodingParts& parts, uint32_t n, uint32_t n_input_dims, const VAL_T* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                                      const float* in, uint32_t in_stride_i, uint32_t in_stride_d, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_d) {
+void encoding_parts_backward(hipStream_t stream, const EncodingParts& parts, uint32_t n, uint32_t n_input_dims, const VAL_T* dL_dy, uint32_t stride_k, uint32_t stride_i,
+                             const float* in, uint32_t in_stride_i, uint32_t in_stride_d, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_d) {
 	if (n == 0 || n_input_dims == 0) return;
 	check_rows("encoding_parts_backward", n, n_input_dims);
 	TCNN_LAUNCH(k_encoding_parts_backward<VAL_T>, dim3(n / CK_THREADS, n_input_dims), dim3(CK_THREADS), 0, stream, parts, n, dL_dy, stride_k, stride_i, in, in_stride_i, in_stride_d,
 	            dL_dx, dx_stride_i, dx_stride_d);
 }
-void encoding_parts_forward(hipStream_t stream, const EncodingParts& parts, uint32_t n, const float* in, uint32_t in_stride_i, uint32_t in_stride_d, half_t* out,
-                            uint32_t stride_k, uint32_t stride_i) {
-	encoding_parts_forward_t<half_t>(stream, parts, n, in, in_stride_i, in_stride_d, out, stride_k, stride_i);
-}
-void encoding_parts_forward(hipStream_t stream, const EncodingParts& parts, uint32_t n, const float* in, uint32_t in_stride_i, uint32_t in_stride_d, float* out,
-                            uint32_t stride_k, uint32_t stride_i) {
-	encoding_parts_forward_t<float>(stream, parts, n, in, in_stride_i, in_stride_d, out, stride_k, stride_i);
-}
-void encoding_parts_backward(hipStream_t stream, const EncodingParts& parts, uint32_t n, uint32_t n_input_dims, const half_t* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                             const float* in, uint32_t in_stride_i, uint32_t in_stride_d, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_d) {
-	encoding_parts_backward_t<half_t>(stream, parts, n, n_input_dims, dL_dy, stride_k, stride_i, in, in_stride_i, in_stride_d, dL_dx, dx_stride_i, dx_stride_d);
-}
-void encoding_parts_backward(hipStream_t stream, const EncodingParts& parts, uint32_t n, uint32_t n_input_dims, const float* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                             const float* in, uint32_t in_stride_i, uint32_t in_stride_d, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_d) {
-	encoding_parts_backward_t<float>(stream, parts, n, n_input_dims, dL_dy, stride_k, stride_i, in, in_stride_i, in_stride_d, dL_dx, dx_stride_i, dx_stride_d);
-}
+TCNN_INSTANTIATE_VALUE_TYPES(encoding_parts_forward)
+TCNN_INSTANTIATE_VALUE_TYPES(encoding_parts_backward)
 
 // ------------------------------------------------------------------------------------------ reductions (composite.h:47-133)
 // Workgroup (x, j): samples [256 x, 256 x + 256) of feature row j; one thread per (row, sample).
@@ -225,8 +197,8 @@ __global__ void __launch_bounds__(CK_THREADS) k_reduce_backward(uint32_t n, uint
 	}
 }
 template <typename T>
-static void reduce_forward_t(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const T* to_reduce, uint32_t stride_k, uint32_t stride_i,
-                             T* reduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i) {
+void reduce_forward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const T* to_reduce, uint32_t stride_k, uint32_t stride_i,
+                    T* reduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i) {
 	if (n == 0 || width == 0) return;
 	check_rows("reduce_forward", n, width);
 	const dim3 grid(n / CK_THREADS, width);
@@ -234,8 +206,8 @@ static void reduce_forward_t(hipStream_t stream, bool product, uint32_t n, uint3
 	else TCNN_LAUNCH((k_reduce_forward<T, false>), grid, dim3(CK_THREADS), 0, stream, n, width, n_to_reduce, to_reduce, stride_k, stride_i, reduced, reduced_stride_k, reduced_stride_i);
 }
 template <typename T>
-static void reduce_backward_t(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const T* to_reduce, T* dL_dunreduced, uint32_t stride_k,
-                              uint32_t stride_i, const T* dL_dreduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i) {
+void reduce_backward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const T* to_reduce, T* dL_dunreduced, uint32_t stride_k,
+                     uint32_t stride_i, const T* dL_dreduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i) {
 	if (n == 0 || width == 0) return;
 	check_rows("reduce_backward", n, width);
 	const dim3 grid(n / CK_THREADS, width);
@@ -246,21 +218,7 @@ static void reduce_backward_t(hipStream_t stream, bool product, uint32_t n, uint
 		TCNN_LAUNCH((k_reduce_backward<T, false>), grid, dim3(CK_THREADS), 0, stream, n, width, n_to_reduce, to_reduce, dL_dunreduced, stride_k, stride_i, dL_dreduced, reduced_stride_k, reduced_stride_i);
 	}
 }
-void reduce_forward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const half_t* to_reduce, uint32_t stride_k, uint32_t stride_i,
-                    half_t* reduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i) {
-	reduce_forward_t<half_t>(stream, product, n, width, n_to_reduce, to_reduce, stride_k, stride_i, reduced, reduced_stride_k, reduced_stride_i);
-}
-void reduce_forward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const float* to_reduce, uint32_t stride_k, uint32_t stride_i,
-                    float* reduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i) {
-	reduce_forward_t<float>(stream, product, n, width, n_to_reduce, to_reduce, stride_k, stride_i, reduced, reduced_stride_k, reduced_stride_i);
-}
-void reduce_backward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const half_t* to_reduce, half_t* dL_dunreduced, uint32_t stride_k,
-                     uint32_t stride_i, const half_t* dL_dreduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i) {
-	reduce_backward_t<half_t>(stream, product, n, width, n_to_reduce, to_reduce, dL_dunreduced, stride_k, stride_i, dL_dreduced, reduced_stride_k, reduced_stride_i);
-}
-void reduce_backward(hipStream_t stream, bool product, uint32_t n, uint32_t width, uint32_t n_to_reduce, const float* to_reduce, float* dL_dunreduced, uint32_t stride_k,
-                     uint32_t stride_i, const float* dL_dreduced, uint32_t reduced_stride_k, uint32_t reduced_stride_i) {
-	reduce_backward_t<float>(stream, product, n, width, n_to_reduce, to_reduce, dL_dunreduced, stride_k, stride_i, dL_dreduced, reduced_stride_k, reduced_stride_i);
-}
+TCNN_INSTANTIATE_VALUE_TYPES(reduce_forward)
+TCNN_INSTANTIATE_VALUE_TYPES(reduce_backward)
 
 }  // namespace tcnn_hip

@@ -128,39 +128,32 @@ void adam_flip_step_representation(hipStream_t stream, uint32_t n, uint32_t step
 // any form -> any form (AdamStepsForm), in place; deficits8 (n bytes) is needed when the byte form is involved
 void adam_convert_step_representation(hipStream_t stream, uint32_t n, uint32_t steps_done, uint32_t* param_steps, uint8_t* deficits8, int from, int to);
 
+// The encodings without parameters.  T, the type of the encoded features and of the incoming gradients, is the library's 16-bit type or float
+// (Encoding<float>: create_encoding(..., Precision::Fp32), cpp_api.cu:165-168 -- nothing is rounded to 16 bits); both are instantiated in
+// elementwise_kernels.hip.
 // encodings/identity.h:46-84.  in: fp32 element (dim j, sample i) at in[i*in_stride_i + j*in_stride_j];
-// out: half element (k, i) at out[k*stride_k + i*stride_i], k < padded, padding value 1.
-void identity_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t padded, float scale, float offset,
-                      const float* in, uint32_t in_stride_i, uint32_t in_stride_j, half_t* out, uint32_t stride_k,
-                      uint32_t stride_i);
-void identity_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, float scale, const half_t* dL_dy, uint32_t stride_k,
-                       uint32_t stride_i, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j);
+// out: element (k, i) at out[k*stride_k + i*stride_i], k < padded, padding value 1.
+template <typename T>
+void identity_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t padded, float scale, float offset, const float* in, uint32_t in_stride_i,
+                      uint32_t in_stride_j, T* out, uint32_t stride_k, uint32_t stride_i);
+template <typename T>
+void identity_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, float scale, const T* dL_dy, uint32_t stride_k, uint32_t stride_i, float* dL_dx,
+                       uint32_t dx_stride_i, uint32_t dx_stride_j);
 
 // encodings/frequency.h:46-104: sin / cos of 2^f pi x, padding value 1; dL/dinput recomputes the derivative the reference stores.
+template <typename T>
 void frequency_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
-                       uint32_t in_stride_j, half_t* out, uint32_t stride_k, uint32_t stride_i);
-void frequency_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const half_t* dL_dy, uint32_t stride_k, uint32_t stride_i,
+                       uint32_t in_stride_j, T* out, uint32_t stride_k, uint32_t stride_i);
+template <typename T>
+void frequency_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const T* dL_dy, uint32_t stride_k, uint32_t stride_i,
                         const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j);
 
 // encodings/oneblob.h:84-164 (n_bins a power of two; padding value 1).  Same addressing conventions as the identity encoding.
+template <typename T>
 void oneblob_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, uint32_t padded, const float* in, uint32_t in_stride_i,
-                     uint32_t in_stride_j, half_t* out, uint32_t stride_k, uint32_t stride_i);
-void oneblob_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, const half_t* dL_dy, uint32_t stride_k, uint32_t stride_i, const float* in,
-                      uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j);
-
-// The same three encodings with fp32 values (Encoding<float>: create_encoding(..., Precision::Fp32), cpp_api.cu:165-168): encoded features
-// and incoming gradients are float, nothing is rounded to 16 bits.
-void identity_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t padded, float scale, float offset, const float* in, uint32_t in_stride_i,
-                      uint32_t in_stride_j, float* out, uint32_t stride_k, uint32_t stride_i);
-void identity_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, float scale, const float* dL_dy, uint32_t stride_k, uint32_t stride_i, float* dL_dx,
-                       uint32_t dx_stride_i, uint32_t dx_stride_j);
-void frequency_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
-                       uint32_t in_stride_j, float* out, uint32_t stride_k, uint32_t stride_i);
-void frequency_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const float* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                        const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j);
-void oneblob_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, uint32_t padded, const float* in, uint32_t in_stride_i,
-                     uint32_t in_stride_j, float* out, uint32_t stride_k, uint32_t stride_i);
-void oneblob_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, const float* dL_dy, uint32_t stride_k, uint32_t stride_i, const float* in,
+                     uint32_t in_stride_j, T* out, uint32_t stride_k, uint32_t stride_i);
+template <typename T>
+void oneblob_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, const T* dL_dy, uint32_t stride_k, uint32_t stride_i, const float* in,
                       uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j);
 
 }  // namespace tcnn_hip

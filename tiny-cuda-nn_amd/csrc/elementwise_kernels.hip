@@ -761,32 +761,28 @@ __global__ void k_identity_backward(uint32_t n, uint32_t n_dims, float scale, co
 	dL_dx[(size_t)i * dx_stride_i + (size_t)k * dx_stride_j] = identity_dL_dx<VAL_T>(dL_dy[(size_t)k * stride_k + (size_t)i * stride_i], scale);
 }
 
+template <typename T>
 void identity_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t padded, float scale, float offset, const float* in,
-                      uint32_t in_stride_i, uint32_t in_stride_j, half_t* out, uint32_t stride_k, uint32_t stride_i) {
+                      uint32_t in_stride_i, uint32_t in_stride_j, T* out, uint32_t stride_k, uint32_t stride_i) {
 	if (n == 0) return;
-	if (in_stride_j == 1 && in_stride_i == n_dims && stride_i == 1 && stride_k == n) {
-		const uint32_t lds = n_dims * ID_LD * (uint32_t)sizeof(half_t);  // 66.5 KB at the widest input (128)
-		TCNN_SET_MAX_DYN_LDS(k_identity_forward_transpose, lds);
-		TCNN_LAUNCH(k_identity_forward_transpose, dim3(div_round_up(n, ID_TILE)), dim3(EW_THREADS), lds, stream, n, n_dims, padded, scale, offset, in, out);
-		return;
+	if constexpr (std::is_same_v<T, half_t>) {
+		if (in_stride_j == 1 && in_stride_i == n_dims && stride_i == 1 && stride_k == n) {
+			const uint32_t lds = n_dims * ID_LD * (uint32_t)sizeof(half_t);  // 66.5 KB at the widest input (128)
+			TCNN_SET_MAX_DYN_LDS(k_identity_forward_transpose, lds);
+			TCNN_LAUNCH(k_identity_forward_transpose, dim3(div_round_up(n, ID_TILE)), dim3(EW_THREADS), lds, stream, n, n_dims, padded, scale, offset, in, out);
+			return;
+		}
 	}
-	TCNN_LAUNCH(k_identity_forward<half_t>, dim3(div_round_up(n * padded, EW_THREADS)), dim3(EW_THREADS), 0, stream, n, n_dims, padded, scale, offset, in, in_stride_i, in_stride_j, out, stride_k, stride_i);
+	TCNN_LAUNCH(k_identity_forward<T>, dim3(div_round_up(n * padded, EW_THREADS)), dim3(EW_THREADS), 0, stream, n, n_dims, padded, scale, offset, in, in_stride_i, in_stride_j, out, stride_k, stride_i);
 }
-void identity_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t padded, float scale, float offset, const float* in,
-                      uint32_t in_stride_i, uint32_t in_stride_j, float* out, uint32_t stride_k, uint32_t stride_i) {
-	if (n == 0) return;
-	TCNN_LAUNCH(k_identity_forward<float>, dim3(div_round_up(n * padded, EW_THREADS)), dim3(EW_THREADS), 0, stream, n, n_dims, padded, scale, offset, in, in_stride_i, in_stride_j, out, stride_k, stride_i);
-}
-void identity_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, float scale, const half_t* dL_dy, uint32_t stride_k, uint32_t stride_i,
+template <typename T>
+void identity_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, float scale, const T* dL_dy, uint32_t stride_k, uint32_t stride_i,
                        float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
 	if (n == 0) return;
-	TCNN_LAUNCH(k_identity_backward<half_t>, dim3(div_round_up(n * n_dims, EW_THREADS)), dim3(EW_THREADS), 0, stream, n, n_dims, scale, dL_dy, stride_k, stride_i, dL_dx, dx_stride_i, dx_stride_j);
+	TCNN_LAUNCH(k_identity_backward<T>, dim3(div_round_up(n * n_dims, EW_THREADS)), dim3(EW_THREADS), 0, stream, n, n_dims, scale, dL_dy, stride_k, stride_i, dL_dx, dx_stride_i, dx_stride_j);
 }
-void identity_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, float scale, const float* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                       float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
-	if (n == 0) return;
-	TCNN_LAUNCH(k_identity_backward<float>, dim3(div_round_up(n * n_dims, EW_THREADS)), dim3(EW_THREADS), 0, stream, n, n_dims, scale, dL_dy, stride_k, stride_i, dL_dx, dx_stride_i, dx_stride_j);
-}
+TCNN_INSTANTIATE_VALUE_TYPES(identity_forward)
+TCNN_INSTANTIATE_VALUE_TYPES(identity_backward)
 
 // ------------------------------------------------------------------------------------------ frequency
 // encodings/frequency.h:46-79, 82-104: output j of sample i = sin(2^f pi x_d + (j & 1) pi / 2), d = j / (2 n_frequencies),
@@ -819,35 +815,21 @@ __global__ void __launch_bounds__(EW_THREADS) k_frequency_backward(uint32_t n, u
 	dL_dx[(size_t)i * dx_stride_i + (size_t)d * dx_stride_j] = frequency_dL_dx<VAL_T>(dL_dy + (size_t)d * outputs_per_input * stride_k + (size_t)i * stride_i, stride_k, n_frequencies, x0);
 }
 template <typename VAL_T>
-static void frequency_forward_t(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
-                                uint32_t in_stride_j, VAL_T* out, uint32_t stride_k, uint32_t stride_i) {
+void frequency_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
+                       uint32_t in_stride_j, VAL_T* out, uint32_t stride_k, uint32_t stride_i) {
 	if (n == 0) return;
 	TCNN_LAUNCH(k_frequency_forward<VAL_T>, dim3(div_round_up(n * padded, EW_THREADS)), dim3(EW_THREADS), 0, stream, n, n_dims, n_frequencies, padded, in, in_stride_i,
 	            in_stride_j, out, stride_k, stride_i);
 }
 template <typename VAL_T>
-static void frequency_backward_t(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const VAL_T* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                                 const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
+void frequency_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const VAL_T* dL_dy, uint32_t stride_k, uint32_t stride_i,
+                        const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
 	if (n == 0) return;
 	TCNN_LAUNCH(k_frequency_backward<VAL_T>, dim3(div_round_up(n * n_dims, EW_THREADS)), dim3(EW_THREADS), 0, stream, n, n_dims, n_frequencies, dL_dy, stride_k, stride_i, in,
 	            in_stride_i, in_stride_j, dL_dx, dx_stride_i, dx_stride_j);
 }
-void frequency_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
-                       uint32_t in_stride_j, half_t* out, uint32_t stride_k, uint32_t stride_i) {
-	frequency_forward_t<half_t>(stream, n, n_dims, n_frequencies, padded, in, in_stride_i, in_stride_j, out, stride_k, stride_i);
-}
-void frequency_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, uint32_t padded, const float* in, uint32_t in_stride_i,
-                       uint32_t in_stride_j, float* out, uint32_t stride_k, uint32_t stride_i) {
-	frequency_forward_t<float>(stream, n, n_dims, n_frequencies, padded, in, in_stride_i, in_stride_j, out, stride_k, stride_i);
-}
-void frequency_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const half_t* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                        const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
-	frequency_backward_t<half_t>(stream, n, n_dims, n_frequencies, dL_dy, stride_k, stride_i, in, in_stride_i, in_stride_j, dL_dx, dx_stride_i, dx_stride_j);
-}
-void frequency_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_frequencies, const float* dL_dy, uint32_t stride_k, uint32_t stride_i,
-                        const float* in, uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
-	frequency_backward_t<float>(stream, n, n_dims, n_frequencies, dL_dy, stride_k, stride_i, in, in_stride_i, in_stride_j, dL_dx, dx_stride_i, dx_stride_j);
-}
+TCNN_INSTANTIATE_VALUE_TYPES(frequency_forward)
+TCNN_INSTANTIATE_VALUE_TYPES(frequency_backward)
 
 // ------------------------------------------------------------------------------------------ one-blob
 // encodings/oneblob.h:84-164 (the SoA kernels' arithmetic) with common_device.h:1076-1095 (quartic kernel).  One thread per
@@ -885,8 +867,8 @@ __global__ void __launch_bounds__(EW_THREADS) k_oneblob_backward(uint32_t n, uin
 }
 
 template <typename VAL_T>
-static void oneblob_forward_t(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, uint32_t padded, const float* in, uint32_t in_stride_i,
-                              uint32_t in_stride_j, VAL_T* out, uint32_t stride_k, uint32_t stride_i) {
+void oneblob_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, uint32_t padded, const float* in, uint32_t in_stride_i,
+                     uint32_t in_stride_j, VAL_T* out, uint32_t stride_k, uint32_t stride_i) {
 	if (n == 0) return;
 	uint32_t log2_bins = 0;
 	while ((1u << log2_bins) < n_bins) ++log2_bins;
@@ -895,29 +877,15 @@ static void oneblob_forward_t(hipStream_t stream, uint32_t n, uint32_t n_dims, u
 	            stride_k, stride_i);
 }
 template <typename VAL_T>
-static void oneblob_backward_t(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, const VAL_T* dL_dy, uint32_t stride_k, uint32_t stride_i, const float* in,
-                               uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
+void oneblob_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, const VAL_T* dL_dy, uint32_t stride_k, uint32_t stride_i, const float* in,
+                      uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
 	if (n == 0) return;
 	uint32_t log2_bins = 0;
 	while ((1u << log2_bins) < n_bins) ++log2_bins;
 	TCNN_LAUNCH(k_oneblob_backward<VAL_T>, dim3(div_round_up(n * n_dims, EW_THREADS)), dim3(EW_THREADS), 0, stream, n, n_dims, log2_bins, dL_dy, stride_k, stride_i, in,
 	            in_stride_i, in_stride_j, dL_dx, dx_stride_i, dx_stride_j);
 }
-void oneblob_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, uint32_t padded, const float* in, uint32_t in_stride_i,
-                     uint32_t in_stride_j, half_t* out, uint32_t stride_k, uint32_t stride_i) {
-	oneblob_forward_t<half_t>(stream, n, n_dims, n_bins, padded, in, in_stride_i, in_stride_j, out, stride_k, stride_i);
-}
-void oneblob_forward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, uint32_t padded, const float* in, uint32_t in_stride_i,
-                     uint32_t in_stride_j, float* out, uint32_t stride_k, uint32_t stride_i) {
-	oneblob_forward_t<float>(stream, n, n_dims, n_bins, padded, in, in_stride_i, in_stride_j, out, stride_k, stride_i);
-}
-void oneblob_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, const half_t* dL_dy, uint32_t stride_k, uint32_t stride_i, const float* in,
-                      uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
-	oneblob_backward_t<half_t>(stream, n, n_dims, n_bins, dL_dy, stride_k, stride_i, in, in_stride_i, in_stride_j, dL_dx, dx_stride_i, dx_stride_j);
-}
-void oneblob_backward(hipStream_t stream, uint32_t n, uint32_t n_dims, uint32_t n_bins, const float* dL_dy, uint32_t stride_k, uint32_t stride_i, const float* in,
-                      uint32_t in_stride_i, uint32_t in_stride_j, float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_j) {
-	oneblob_backward_t<float>(stream, n, n_dims, n_bins, dL_dy, stride_k, stride_i, in, in_stride_i, in_stride_j, dL_dx, dx_stride_i, dx_stride_j);
-}
+TCNN_INSTANTIATE_VALUE_TYPES(oneblob_forward)
+TCNN_INSTANTIATE_VALUE_TYPES(oneblob_backward)
 
 }  // namespace tcnn_hip

@@ -439,7 +439,7 @@ void grid_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, c
 }
 
 // ---- fp32 encodings (GridEncodingTemplated<float>) ----
-void grid_backward_f32(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, float* grid_gradient, bool accumulate) {
+void grid_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, float* grid_gradient, bool accumulate) {
 	if (io.n == 0) return;
 	if (!grid_gradient) throw std::runtime_error("grid_backward: missing gradient buffer");
 	const size_t n_params = (size_t)meta.offset[meta.n_levels] * meta.n_feat;

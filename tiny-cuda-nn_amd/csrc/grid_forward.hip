@@ -435,7 +435,7 @@ void grid_forward(hipStream_t stream, const GridMeta& meta, const GridIO& io, co
 }
 
 // ---- fp32 encodings (GridEncodingTemplated<float>) ----
-void grid_forward_f32(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* params, float* out, float* dy_dx) {
+void grid_forward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* params, float* out, float* dy_dx) {
 	if (io.n == 0) return;
 	const uint32_t blocks = grid_n_blocks(meta.n_levels, io.n);
 	grid_dispatch(meta, [&](auto D, auto F) {

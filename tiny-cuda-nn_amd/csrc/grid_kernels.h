@@ -98,12 +98,13 @@ void grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_feature
                          const half_t* dL_dy, const float* dy_dx, float* dL_dx, uint32_t dx_stride_i,
                          uint32_t dx_stride_d);
 
-// ---- fp32 encodings: GridEncodingTemplated<float> (cpp_api.cu:165-168).  Parameters / encoded features / gradients fp32, the reference's
-// formulation (fp32 fma interpolation, one fp32 global atomic per corner and feature); same GridIO addressing as above.
-void grid_forward_f32(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* params, float* out, float* dy_dx = nullptr);
-void grid_backward_f32(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, float* grid_gradient, bool accumulate);
-void grid_backward_input_f32(hipStream_t stream, uint32_t n_dims, uint32_t n_features, const GridIO& io, const float* dL_dy, const float* dy_dx, float* dL_dx,
-                             uint32_t dx_stride_i, uint32_t dx_stride_d);
+// ---- fp32 encodings: GridEncodingTemplated<float> (cpp_api.cu:165-168), the overloads on float.  Parameters / encoded features / gradients
+// fp32, the reference's formulation (fp32 fma interpolation, one fp32 global atomic per corner and feature); same GridIO addressing as above.
+// That backward has one formulation: no mode, no LDS budget, no workspace.
+void grid_forward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* params, float* out, float* dy_dx = nullptr);
+void grid_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, float* grid_gradient, bool accumulate);
+void grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_features, const GridIO& io, const float* dL_dy, const float* dy_dx, float* dL_dx,
+                         uint32_t dx_stride_i, uint32_t dx_stride_d);
 
 // ---- second order: gradients of dL_dx = sum_k dL_dy[k] * dy_dx[k] (the first backward's input gradient) --------------
 // (grid.h:352-655, 910-1042: what SDF / eikonal losses differentiate through)
@@ -118,11 +119,11 @@ void grid_backward_backward_dLdoutput(hipStream_t stream, uint32_t n_dims, uint3
 void grid_backward_backward_input(hipStream_t stream, const GridMeta& meta, const GridIO& io, const half_t* dL_dy, const half_t* params,
                                   float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_d);
 // The same three for an fp32 encoding (the reference's T = float instances of these kernels): fp32 parameters, dL_dy and results, nothing
-// rounded through 16 bits.  The parameter part is grid_backward_f32() with io.ddx set (one fp32 global atomic per corner and feature).
+// rounded through 16 bits.  The parameter part is the fp32 grid_backward() with io.ddx set (one fp32 global atomic per corner and feature).
 void grid_backward_backward_dLdoutput(hipStream_t stream, uint32_t n_dims, uint32_t n_features, uint32_t n_to_pad, const GridIO& io, const float* dy_dx,
                                       float* dL_ddLdy);
-void grid_backward_backward_input_f32(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, const float* params, float* dL_dx,
-                                      uint32_t dx_stride_i, uint32_t dx_stride_d);
+void grid_backward_backward_input(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, const float* params, float* dL_dx,
+                                  uint32_t dx_stride_i, uint32_t dx_stride_d);
 
 // Debug/parity helper: entry index per (sample, level, corner) -> indices[(i*L + l)*2^D + c]
 void grid_indices(hipStream_t stream, const GridMeta& meta, const GridIO& io, uint32_t* indices);

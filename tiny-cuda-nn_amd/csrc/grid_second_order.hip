@@ -168,7 +168,7 @@ void grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_feature
 	            dL_dx, dx_stride_i, dx_stride_d);
 }
 
-void grid_backward_input_f32(hipStream_t stream, uint32_t n_dims, uint32_t n_features, const GridIO& io, const float* dL_dy, const float* dy_dx, float* dL_dx,
+void grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_features, const GridIO& io, const float* dL_dy, const float* dy_dx, float* dL_dx,
                              uint32_t dx_stride_i, uint32_t dx_stride_d) {
 	if (io.n == 0) return;
 	TCNN_LAUNCH(k_grid_backward_input<float>, dim3(div_round_up(io.n, 128u)), dim3(128), 0, stream, n_dims, n_features, io, dL_dy, dy_dx, dL_dx, dx_stride_i,
@@ -199,7 +199,7 @@ void grid_backward_backward_dLdoutput(hipStream_t stream, uint32_t n_dims, uint3
 	TCNN_LAUNCH(k_grid_backward_backward_dLdoutput_f32, dim3(div_round_up(io.n, 128u)), dim3(128), 0, stream, n_dims, n_features, n_to_pad, io, dy_dx, dL_ddLdy);
 }
 
-void grid_backward_backward_input_f32(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, const float* params, float* dL_dx,
+void grid_backward_backward_input(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, const float* params, float* dL_dx,
                                       uint32_t dx_stride_i, uint32_t dx_stride_d) {
 	if (io.n == 0) return;
 	if (!io.ddx) throw std::runtime_error("grid second-order pass: dL_ddLdinput is required");

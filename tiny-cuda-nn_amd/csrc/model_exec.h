@@ -55,14 +55,53 @@ struct LevelGroups {
 int refuse_max_level(const Model& md);
 void check_batch(uint32_t n, uint32_t widest = 128);
 uint32_t widest_matrix(const Model& md);  // the widest matrix any pass over `md` indexes, in elements per sample
-// Encoding forward into a feature-major (SoA) or sample-major (AoS) half matrix.  dy_dx: a lone grid's; a Composite keeps what its backward
-// pass needs in `ctx` (null: inference), its nested grids' dy_dx when prepare_input_gradients is set.
-void encoding_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const half_t* enc_params, half_t* out,
-                      bool soa, float* dy_dx, ForwardCtx* ctx = nullptr, bool prepare_input_gradients = false);
-// the encoding's share of the backward pass: dL_denc has element (feature k, sample i) at [k * stride_k + i * stride_i]
-void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const half_t* dL_denc,
-                       uint32_t stride_k, uint32_t stride_i, half_t* dL_dparams, bool want_grads, bool accumulate, const float* input,
-                       uint32_t lds_level_budget, const LevelGroups* groups = nullptr);
+
+// One grid's slice of a pass, the same for a lone grid and for one nested in a Composite: positions from input dim dims_to_encode_begin on; the
+// encoded matrix (or dL_dy) as the grid sees it, i.e. the caller hands the kernels its matrix from row output_row on.  A lone grid also carries
+// its max_level state (the encoding's own in a forward pass, the context's in every pass behind it); nested grids have none.
+struct GridSlice {
+	GridMeta grid;
+	GridIO io;
+	GridSlice& max_level(float value, const float* per_sample) {
+		grid.max_level = value;
+		io.max_level = per_sample;
+		return *this;
+	}
+};
+inline GridSlice grid_slice(const EncodingDesc& g, const IoLayout& layout, const float* input, uint32_t n, uint32_t stride_k, uint32_t stride_i) {
+	return {g.grid, {input + (size_t)g.dims_to_encode_begin * layout.in_stride_d, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i}};
+}
+// grid_backward reports its kernels one by one (GridBackwardWorkspace::phase_hook): the pass's timer, for the profiler's two backward stages
+struct PhaseTimer {
+	Profiler* profiler;
+	hipStream_t stream;
+	bool counts = true;  // false once the step's first launch sequence is out: later ones (level groups, further grids) add time, not launches
+	hipEvent_t a = nullptr;  // the open phase's first event
+};
+// The 16-bit parameter gradients of one grid slice: takes the backward's workspace (scratch, zeroed counters, the timer's hook) and runs
+// grid_backward.  With `groups` the levels go in ranges -- one workspace, sized to the largest -- and `ready` is called per range, the
+// parameter range counted from `first_param`.
+void grid_backward_with_workspace(hipStream_t stream, const GridSlice& s, const half_t* dL_dy, half_t* grid_gradient, bool accumulate, GridBackwardMode mode,
+                                  uint32_t lds_level_budget, PhaseTimer* timer = nullptr, const LevelGroups* groups = nullptr, size_t first_param = 0);
+
+// What the caller of a pass states first, once: the batch guards (false: an empty batch, nothing to do).  A forward pass files the batch in
+// its context (stream, n, the lone grid's max_level state); a backward pass checks the batch against the context it was given.
+bool begin_pass(hipStream_t stream, const Model& md, uint32_t n, ForwardCtx* ctx = nullptr);
+bool begin_backward(const Model& md, const ForwardCtx& ctx, uint32_t n);
+// Encoding forward, T = the 16-bit type or float (Encoding<float>, which computes in fp32): `out` has element (feature k, sample i) at
+// [k * stride_k + i * stride_i] -- feature-major (stride_k = n, stride_i = 1) in front of a network, sample-major (1, padded width) bare.
+// Leaves in `ctx` (null: inference) what the backward pass needs: dy_dx when prepare_input_gradients is set, a Composite's unreduced
+// matrix.  The caller has been through begin_pass (model_forward, the trainer's fused step, the fp32 module entries).
+template <typename T>
+void encoding_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const T* enc_params, T* out,
+                      uint32_t stride_k, uint32_t stride_i, ForwardCtx* ctx = nullptr, bool prepare_input_gradients = false);
+// the encoding's share of the backward pass: dL_denc has element (feature k, sample i) at [k * stride_k + i * stride_i]; dL_dparams is the
+// model's (the encoding's behind the network's).  The fp32 grid backward has one formulation: budget and groups are the 16-bit one's.
+// The caller has been through begin_backward (model_backward, the fp32 module entry) or made `ctx` itself in this call (the fused step).
+template <typename T>
+void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const T* dL_denc,
+                       uint32_t stride_k, uint32_t stride_i, T* dL_dparams, bool want_grads, bool accumulate, const float* input,
+                       uint32_t lds_level_budget = 0, const LevelGroups* groups = nullptr);
 // The caller's own 16-bit input / dL_dinput matrices (tcnn_module_*_half_input; dense [n][n_input_dims] in the library's 16-bit type) go to
 // exactly the modules tcnn_create_network makes: a network behind an Identity encoding with scale 1 and offset 0, which is exact on values of
 // that type.  Why `md` is not one of them (empty: it is); refuse_half_input sets that as the last error and returns TCNN_ERROR_UNSUPPORTED.
@@ -78,10 +117,5 @@ void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, con
                     uint32_t lds_level_budget, half_t* dL_dinput16 = nullptr);  // dL_dinput16: of a context made with input16, instead of dL_dinput
 // network->inference into the caller's fp32 matrix (object.h:214-271)
 void inference_to_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const half_t* params, float* out, uint32_t stride_i, uint32_t stride_j);
-// Encoding<float>: a bare encoding that computes in fp32 (model_exec.hip)
-void encoding_forward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const float* params, float* out, ForwardCtx* ctx,
-                          bool prepare_input_gradients);
-void encoding_backward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const float* dL_doutput, float* dL_dparams,
-                           const float* input);
 
 }  // namespace tcnn_hip

@@ -2,7 +2,6 @@
 #include "model_exec.h"
 
 #include <algorithm>
-#include <vector>
 
 #include "half_input_kernels.h"
 #include "host_common.h"
@@ -96,15 +95,30 @@ static EncodingParts parameterless_parts(const EncodingDesc& c) {
 	}
 	return parts;
 }
-static void nested_grid_forward(hipStream_t stream, const GridMeta& g, const GridIO& io, const half_t* params, half_t* out, float* dy_dx) { grid_forward(stream, g, io, params, out, dy_dx); }
-static void nested_grid_forward(hipStream_t stream, const GridMeta& g, const GridIO& io, const float* params, float* out, float* dy_dx) { grid_forward_f32(stream, g, io, params, out, dy_dx); }
-static void nested_grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_features, const GridIO& io, const half_t* dL_dy, const float* dy_dx, float* dL_dx,
-                                       uint32_t dx_stride_i, uint32_t dx_stride_d) {
-	grid_backward_input(stream, n_dims, n_features, io, dL_dy, dy_dx, dL_dx, dx_stride_i, dx_stride_d);
+
+// ---- the steps of one grid, lone or nested.  `rows` / `dL_dy`: the pass's matrix from the grid's first row (output_row) on.
+// forward; the padded features behind the grid's own are zero (grid.h:757-766)
+template <typename T>
+static void grid_forward_padded(hipStream_t stream, const EncodingDesc& g, const GridSlice& s, const T* params, T* rows, float* dy_dx) {
+	grid_forward(stream, s.grid, s.io, params, rows, dy_dx);
+	const uint32_t n_to_pad = g.padded_output_width - g.n_output_dims;
+	if (n_to_pad == 0) return;
+	if (s.io.stride_k == 1u) {  // sample-major: n_to_pad columns of every sample's row
+		HIP_CHECK(hipMemset2DAsync(rows + g.n_output_dims, (size_t)s.io.stride_i * sizeof(T), 0, (size_t)n_to_pad * sizeof(T), s.io.n, stream));
+	} else {  // feature-major: n_to_pad whole rows
+		HIP_CHECK(hipMemsetAsync(rows + (size_t)g.n_output_dims * s.io.stride_k, 0, (size_t)n_to_pad * s.io.stride_k * sizeof(T), stream));
+	}
 }
-static void nested_grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_features, const GridIO& io, const float* dL_dy, const float* dy_dx, float* dL_dx,
-                                       uint32_t dx_stride_i, uint32_t dx_stride_d) {
-	grid_backward_input_f32(stream, n_dims, n_features, io, dL_dy, dy_dx, dL_dx, dx_stride_i, dx_stride_d);
+// the fp32 dy_dx of one grid for a pass that prepares input gradients ([(k * n + i) * D + d], grid.h:783-785), kept in `slot`
+static float* take_dy_dx(hipStream_t stream, const EncodingDesc& g, uint32_t n, Scratch& slot) {
+	slot = Scratch(stream, (size_t)g.n_output_dims * n * g.n_dims * sizeof(float));
+	return slot.as<float>();
+}
+template <typename T>
+static void grid_input_gradients(hipStream_t stream, const EncodingDesc& g, const IoLayout& layout, const GridSlice& s, const T* dL_dy, const Scratch& dy_dx, float* dL_dinput) {
+	if (!dy_dx.ptr) throw std::runtime_error("backward: dL_dinput requested but forward was not run with prepare_input_gradients");
+	grid_backward_input(stream, g.n_dims, g.n_output_dims, s.io, dL_dy, (const float*)dy_dx.ptr, dL_dinput + (size_t)g.dims_to_encode_begin * layout.dx_stride_d, layout.dx_stride_i,
+	                    layout.dx_stride_d);
 }
 
 // out: element (feature k, sample i) at [k * stride_k + i * stride_i] with stride_i == 1 (feature-major) or stride_k == 1 (sample-major, stride_i = the padded width)
@@ -131,22 +145,8 @@ static void composite_forward(hipStream_t stream, const EncodingDesc& c, const I
 	for (size_t idx = 0; idx < c.nested.size(); ++idx) {
 		const EncodingDesc& e = c.nested[idx];
 		if (!e.is_grid()) continue;
-		float* dy_dx = nullptr;
-		if (ctx && prepare_input_gradients) {
-			ctx->nested_dy_dx[idx] = Scratch(stream, (size_t)e.n_output_dims * n * e.n_dims * sizeof(float));
-			dy_dx = ctx->nested_dy_dx[idx].template as<float>();
-		}
-		GridIO io = {input + (size_t)e.dims_to_encode_begin * layout.in_stride_d, layout.in_stride_i, layout.in_stride_d, n, stride_k, target_stride_i};
-		T* rows = target + (size_t)e.output_row * stride_k;
-		nested_grid_forward(stream, e.grid, io, enc_params + e.param_offset, rows, dy_dx);
-		const uint32_t n_to_pad = e.padded_output_width - e.n_output_dims;
-		if (n_to_pad > 0) {  // grid.h:757-766: padded dims are zero
-			if (stride_k == 1u) {
-				HIP_CHECK(hipMemset2DAsync(rows + e.n_output_dims, (size_t)target_stride_i * sizeof(T), 0, (size_t)n_to_pad * sizeof(T), n, stream));
-			} else {
-				HIP_CHECK(hipMemsetAsync(rows + (size_t)e.n_output_dims * stride_k, 0, (size_t)n_to_pad * stride_k * sizeof(T), stream));
-			}
-		}
+		float* dy_dx = ctx && prepare_input_gradients ? take_dy_dx(stream, e, n, ctx->nested_dy_dx[idx]) : nullptr;
+		grid_forward_padded(stream, e, grid_slice(e, layout, input, n, stride_k, target_stride_i), enc_params + e.param_offset, target + (size_t)e.output_row * stride_k, dy_dx);
 	}
 	if (reduce) reduce_forward(stream, c.reduction == ReductionType::Product, n, c.padded_output_width, (uint32_t)c.nested.size(), (const T*)target, stride_k, target_stride_i, out, stride_k, stride_i);
 }
@@ -173,39 +173,39 @@ static const T* composite_backward_input(hipStream_t stream, const EncodingDesc&
 		for (size_t idx = 0; idx < c.nested.size(); ++idx) {
 			const EncodingDesc& e = c.nested[idx];
 			if (!e.is_grid()) continue;
-			if (idx >= ctx.nested_dy_dx.size() || !ctx.nested_dy_dx[idx].ptr) throw std::runtime_error("backward: dL_dinput requested but forward was not run with prepare_input_gradients");
-			GridIO io = {input + (size_t)e.dims_to_encode_begin * layout.in_stride_d, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
-			nested_grid_backward_input(stream, e.n_dims, e.n_output_dims, io, dL_denc + (size_t)e.output_row * stride_k, (const float*)ctx.nested_dy_dx[idx].ptr,
-			                           dL_dinput + (size_t)e.dims_to_encode_begin * layout.dx_stride_d, layout.dx_stride_i, layout.dx_stride_d);
+			if (idx >= ctx.nested_dy_dx.size()) throw std::runtime_error("backward: dL_dinput requested but forward was not run with prepare_input_gradients");
+			grid_input_gradients(stream, e, layout, grid_slice(e, layout, input, n, stride_k, stride_i), dL_denc + (size_t)e.output_row * stride_k, ctx.nested_dy_dx[idx], dL_dinput);
 		}
 	}
 	return dL_denc;
 }
 
-// Encoding forward into a feature-major (SoA) or sample-major (AoS) half matrix.
-void encoding_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const half_t* enc_params, half_t* out,
-                             bool soa, float* dy_dx, ForwardCtx* ctx, bool prepare_input_gradients) {
+bool begin_pass(hipStream_t stream, const Model& md, uint32_t n, ForwardCtx* ctx) {
+	check_batch(n, widest_matrix(md));
+	if (n == 0) return false;
+	if (ctx) {
+		ctx->stream = stream;
+		ctx->n = n;
+		ctx->keep_max_level(md.enc);
+	}
+	return true;
+}
+
+template <typename T>
+void encoding_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const T* enc_params, T* out,
+                      uint32_t stride_k, uint32_t stride_i, ForwardCtx* ctx, bool prepare_input_gradients) {
 	const EncodingDesc& e = md.enc;
-	const uint32_t stride_k = soa ? n : 1u, stride_i = soa ? 1u : e.padded_output_width;
 	ProfScope prof(profiler, stream, STAGE_GRID_FWD);
 	if (e.is_composite()) {
 		composite_forward(stream, e, layout, n, input, enc_params, out, stride_k, stride_i, ctx, prepare_input_gradients);
 	} else if (e.is_grid()) {
-		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
-		io.max_level = e.max_level_gpu;
-		grid_forward(stream, e.grid, io, enc_params, out, dy_dx);
-		const uint32_t n_to_pad = e.padded_output_width - e.n_output_dims;
-		if (n_to_pad > 0) {  // grid.h:757-766: padded dims are zero
-			if (soa) {
-				HIP_CHECK(hipMemsetAsync(out + (size_t)e.n_output_dims * n, 0, (size_t)n_to_pad * n * sizeof(half_t), stream));
-			} else {
-				HIP_CHECK(hipMemset2DAsync(out + e.n_output_dims, (size_t)e.padded_output_width * sizeof(half_t), 0, (size_t)n_to_pad * sizeof(half_t), n, stream));
-			}
-		}
+		float* dy_dx = ctx && prepare_input_gradients ? take_dy_dx(stream, e, n, ctx->dy_dx) : nullptr;
+		grid_forward_padded(stream, e, grid_slice(e, layout, input, n, stride_k, stride_i).max_level(e.grid.max_level, e.max_level_gpu), enc_params, out, dy_dx);
 	} else {
 		parameterless_forward(stream, e, layout, n, input, out, stride_k, stride_i);
 	}
 }
+TCNN_INSTANTIATE_VALUE_TYPES(encoding_forward)
 
 // (mlp_train_supported is false for every mlp_layer_by_layer() network: those always save their activations)
 static bool backward_recomputes(const Model& md) { return g_fused_network_passes.load() != 0 && md.has_network && mlp_train_supported(md.net.mlp); }
@@ -213,22 +213,11 @@ static bool backward_recomputes(const Model& md) { return g_fused_network_passes
 // NetworkWithInputEncoding::forward_impl / inference_mixed_precision_impl (:60-81).  ctx == nullptr: inference.
 void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, half_t* output, const half_t* params,
                           ForwardCtx* ctx, bool prepare_input_gradients, const MlpF32Output* f32, const half_t* input16) {
-	check_batch(n, widest_matrix(md));
 	if (input16 && !half_input_refusal(md).empty()) throw std::runtime_error(half_input_refusal(md));
 	if (ctx) ctx->half_input = input16 != nullptr;
-	if (n == 0) return;
-	if (ctx) {
-		ctx->stream = stream;
-		ctx->n = n;
-		ctx->keep_max_level(md.enc);
-	}
-	float* dy_dx = nullptr;
-	if (ctx && prepare_input_gradients && md.enc.is_grid()) {
-		ctx->dy_dx = Scratch(stream, (size_t)md.enc.n_output_dims * n * md.n_input_dims * sizeof(float));
-		dy_dx = ctx->dy_dx.as<float>();
-	}
-	if (!md.has_network) {
-		encoding_forward(stream, profiler, md, layout, n, input, params, output, /*soa=*/false, dy_dx, ctx, prepare_input_gradients);
+	if (!begin_pass(stream, md, n, ctx)) return;
+	if (!md.has_network) {  // the bare encoding's output is sample-major (cpp_api.cu:94-95)
+		encoding_forward(stream, profiler, md, layout, n, input, params, output, 1u, md.enc.padded_output_width, ctx, prepare_input_gradients);
 		return;
 	}
 	// inference into the caller's fp32 matrix with an Identity encoding that pads nothing: the inference kernel reads the fp32 input itself
@@ -252,7 +241,7 @@ void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, cons
 		ProfScope prof_enc(profiler, stream, STAGE_GRID_FWD);
 		half_input_pad(stream, n, e.n_dims, e.padded_output_width, (const uint16_t*)input16, (uint16_t*)enc.ptr, half_bits(1.0f));
 	} else {
-		encoding_forward(stream, profiler, md, layout, n, input, params + md.n_mlp_params(), enc.as<half_t>(), /*soa=*/true, dy_dx, ctx, prepare_input_gradients);
+		encoding_forward(stream, profiler, md, layout, n, input, params + md.n_mlp_params(), enc.as<half_t>(), n, 1u, ctx, prepare_input_gradients);
 	}
 	half_t* hidden = nullptr;
 	if (ctx && !backward_recomputes(md)) {
@@ -293,13 +282,17 @@ uint32_t widest_matrix(const Model& md) {
 	return w;
 }
 
+bool begin_backward(const Model& md, const ForwardCtx& ctx, uint32_t n) {
+	if (!begin_pass(nullptr, md, n)) return false;
+	if (ctx.n != n) throw std::runtime_error("backward: batch size does not match the forward context");
+	return true;
+}
+
 // NetworkWithInputEncoding::backward_impl (:83-113) / GridEncodingTemplated::backward_impl (grid.h:817-908)
 void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const half_t* dL_doutput,
                            half_t* dL_dparams, const float* input, const half_t* output, const half_t* params, int gradient_mode,
                            uint32_t lds_level_budget, half_t* dL_dinput16) {
-	check_batch(n, widest_matrix(md));
-	if (n == 0) return;
-	if (ctx.n != n) throw std::runtime_error("backward: batch size does not match the forward context");
+	if (!begin_backward(md, ctx, n)) return;
 	if (dL_dinput16 && (dL_dinput || !ctx.half_input)) throw std::runtime_error("backward: a 16-bit dL_dinput belongs to a context made with a 16-bit input");
 	const bool recompute = md.has_network && !ctx.hidden.ptr;  // the context holds the encoded input only (see g_fused_network_passes)
 	if (recompute && (!ctx.enc.ptr || !mlp_train_supported(md.net.mlp))) {
@@ -364,14 +357,6 @@ void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, con
 	encoding_share(dL_denc, stride_k, stride_i);
 }
 
-// the encoding's share of the backward pass: dL_denc has element (feature k, sample i) at [k * stride_k + i * stride_i]
-// grid_backward reports its kernels one by one (GridBackwardWorkspace::phase_hook); user = the pass's PhaseTimer
-struct PhaseTimer {
-	Profiler* profiler;
-	hipStream_t stream;
-	bool counts;  // false while the level groups after the first are launched: their time adds to the stage, the launch count of the step does not
-	hipEvent_t a = nullptr;  // the open phase's first event
-};
 static void grid_backward_phase_hook(void* user, int phase, int begin) {
 	PhaseTimer& t = *(PhaseTimer*)user;
 	Profiler* p = t.profiler;
@@ -401,169 +386,106 @@ static GridMeta grid_levels(const GridMeta& g, uint32_t a, uint32_t b) {
 }
 
 // consecutive levels in `n_groups` groups, cut where the running parameter count passes k / n_groups of the total
-static std::vector<std::pair<uint32_t, uint32_t>> split_levels(const GridMeta& g, uint32_t n_groups) {
+struct LevelRanges {
+	uint32_t n = 0;
+	uint32_t begin[MAX_N_LEVELS], end[MAX_N_LEVELS];
+};
+static LevelRanges split_levels(const GridMeta& g, uint32_t n_groups) {
 	const uint32_t L = g.n_levels;
-	std::vector<std::pair<uint32_t, uint32_t>> level_ranges;
+	LevelRanges ranges;
 	for (uint32_t k = 1, a = 0; k <= n_groups && a < L; ++k) {
 		uint32_t b = a + 1;
 		const uint64_t target = (uint64_t)g.offset[L] * k / n_groups;
 		while (b < L && (k == n_groups || g.offset[b] < target)) ++b;
 		if (k == n_groups) b = L;
-		level_ranges.push_back({a, b});
+		ranges.begin[ranges.n] = a;
+		ranges.end[ranges.n++] = b;
 		a = b;
 	}
-	return level_ranges;
+	return ranges;
 }
 
-void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const half_t* dL_denc,
-                              uint32_t stride_k, uint32_t stride_i, half_t* dL_dparams, bool want_grads, bool accumulate, const float* input,
-                              uint32_t lds_level_budget, const LevelGroups* groups) {
+void grid_backward_with_workspace(hipStream_t stream, const GridSlice& s, const half_t* dL_dy, half_t* grid_gradient, bool accumulate, GridBackwardMode mode,
+                                  uint32_t lds_level_budget, PhaseTimer* timer, const LevelGroups* groups, size_t first_param) {
+	const GridMeta& grid = s.grid;
+	const uint32_t L = grid.n_levels, F = grid.n_feat, n = s.io.n;
+	// level groups: only where a level's treatment does not depend on its index among ALL levels (every level switched on,
+	// no per-level random stream) and nothing else rides on the pass
+	uint32_t n_groups = groups ? std::min(std::max(groups->n_groups, 1u), L) : 1u;
+	if (grid.max_level < 1.0f || s.io.max_level || grid.stochastic != 0u) n_groups = 1;
+	const LevelRanges ranges = split_levels(grid, n_groups);
+	// one workspace for all groups: the largest any of them asks for (a group of later levels can bucket levels that the plan of
+	// the whole grid, which takes the first MAX_BUCKET_LEVELS eligible ones, left to the other kinds)
+	GridBackwardWorkspace ws;
+	if (ranges.n <= 1) ws = grid_backward_workspace_size(grid, n, mode, lds_level_budget);
+	for (uint32_t r = 0; ranges.n > 1 && r < ranges.n; ++r) {
+		const GridBackwardWorkspace w = grid_backward_workspace_size(grid_levels(grid, ranges.begin[r], ranges.end[r]), n, mode, lds_level_budget);
+		ws.scratch_bytes = std::max(ws.scratch_bytes, w.scratch_bytes);
+		ws.n_counters = std::max(ws.n_counters, w.n_counters);
+	}
+	Scratch queues;
+	if (ws.scratch_bytes) {
+		queues = Scratch(stream, ws.scratch_bytes);
+		ws.scratch = queues.ptr;
+		ws.scratch_bytes = queues.bytes;
+		ws.counters = ZeroedCounters::get(stream, ws.n_counters);
+	}
+	if (timer) {  // per-kernel timing when a profiler is attached
+		ws.phase_hook = grid_backward_phase_hook;
+		ws.hook_user = timer;
+	}
+	// Overwrite vs Accumulate (grid.h:865-867) is handled inside: the owner-computes kernel stores whole slices, so the reference's
+	// full-table memset is only issued for the atomic A/B mode.
+	for (uint32_t r = 0; r < std::max(ranges.n, 1u); ++r) {
+		const uint32_t a = ranges.n > 1 ? ranges.begin[r] : 0u, b = ranges.n > 1 ? ranges.end[r] : L;
+		grid_backward(stream, ranges.n > 1 ? grid_levels(grid, a, b) : grid, s.io, dL_dy + (size_t)a * F * s.io.stride_k, grid_gradient + (size_t)grid.offset[a] * F, accumulate, mode,
+		              lds_level_budget, ws);
+		if (timer) timer->counts = false;  // one backward pass per step, however many launch sequences it takes
+		if (groups && groups->ready) groups->ready(groups->ctx, first_param + (size_t)grid.offset[a] * F, first_param + (size_t)grid.offset[b] * F);
+	}
+}
+
+// One grid's parameter gradients in the pass's value type.  16-bit: the chosen backward mode with its LDS budget and workspace, level groups
+// with the `ready` callback, the profiler's stages.  fp32: the reference's one formulation has none of them.
+static void grid_parameter_gradients(hipStream_t stream, PhaseTimer& timer, const GridSlice& s, const half_t* dL_dy, half_t* grid_gradient, bool accumulate, uint32_t lds_level_budget,
+                                     const LevelGroups* groups, size_t first_param) {
+	grid_backward_with_workspace(stream, s, dL_dy, grid_gradient, accumulate, (GridBackwardMode)g_grid_backward_mode.load(), lds_level_budget, &timer, groups, first_param);
+}
+static void grid_parameter_gradients(hipStream_t stream, PhaseTimer&, const GridSlice& s, const float* dL_dy, float* grid_gradient, bool accumulate, uint32_t, const LevelGroups*, size_t) {
+	grid_backward(stream, s.grid, s.io, dL_dy, grid_gradient, accumulate);
+}
+
+// The encoding's share of the backward pass, from dL/d(encoded input) -- the feature-major matrix the network kernels wrote, or a bare
+// encoding's sample-major dL_doutput: dL_denc has element (feature k, sample i) at [k * stride_k + i * stride_i].
+template <typename T>
+void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const T* dL_denc,
+                       uint32_t stride_k, uint32_t stride_i, T* dL_dparams, bool want_grads, bool accumulate, const float* input, uint32_t lds_level_budget,
+                       const LevelGroups* groups) {
 	const EncodingDesc& e = md.enc;
+	want_grads = want_grads && dL_dparams && e.n_params > 0;
+	T* enc_grads = want_grads ? dL_dparams + md.n_mlp_params() : nullptr;
+	PhaseTimer timer = {profiler, stream};
 	if (e.is_composite()) {
 		Scratch dL_dunreduced;
 		dL_denc = composite_backward_input(stream, e, layout, ctx, n, md.n_input_dims, dL_dinput, dL_denc, stride_k, stride_i, input, dL_dunreduced);
-		if (want_grads && e.n_params > 0) {
-			// every nested grid on its own slice of dL_dy, its gradients at its own parameter offset: Overwrite / Accumulate hold per slice, the
-			// bucketed backward's workspace is requested per grid (the plain path: no level groups)
-			const GridBackwardMode mode = (GridBackwardMode)g_grid_backward_mode.load();
-			if (lds_level_budget == 0) lds_level_budget = g_default_lds_slice_bytes;
-			PhaseTimer timer = {profiler, stream, /*counts=*/true};
-			for (const EncodingDesc& g : e.nested) {
-				if (!g.is_grid() || g.n_params == 0) continue;
-				GridIO io = {input + (size_t)g.dims_to_encode_begin * layout.in_stride_d, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
-				GridBackwardWorkspace ws = grid_backward_workspace_size(g.grid, n, mode, lds_level_budget);
-				Scratch queues;
-				if (ws.scratch_bytes) {
-					queues = Scratch(stream, ws.scratch_bytes);
-					ws.scratch = queues.ptr;
-					ws.scratch_bytes = queues.bytes;
-					ws.counters = ZeroedCounters::get(stream, ws.n_counters);
-				}
-				ws.phase_hook = grid_backward_phase_hook;
-				ws.hook_user = &timer;
-				grid_backward(stream, g.grid, io, dL_denc + (size_t)g.output_row * stride_k, dL_dparams + md.n_mlp_params() + g.param_offset, accumulate, mode, lds_level_budget, ws);
-				timer.counts = false;  // one backward pass per step, however many grids it has
-			}
-			if (groups && groups->ready) groups->ready(groups->ctx, md.n_mlp_params(), md.n_params());
+		if (!want_grads) return;
+		// every nested grid on its own slice of dL_dy, its gradients at its own parameter offset: Overwrite / Accumulate hold per slice, the
+		// workspace is taken per grid (the plain path: no level groups)
+		for (const EncodingDesc& g : e.nested) {
+			if (!g.is_grid() || g.n_params == 0) continue;
+			grid_parameter_gradients(stream, timer, grid_slice(g, layout, input, n, stride_k, stride_i), dL_denc + (size_t)g.output_row * stride_k, enc_grads + g.param_offset, accumulate,
+			                         lds_level_budget, nullptr, 0);
 		}
+		if (groups && groups->ready) groups->ready(groups->ctx, md.n_mlp_params(), md.n_params());
 	} else if (e.is_grid()) {
-		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
-		io.max_level = ctx.max_level_gpu;  // max_level as the forward pass of this context saw it
-		GridMeta grid = e.grid;
-		grid.max_level = ctx.max_level;
-		if (want_grads && e.n_params > 0) {
-			half_t* grid_grads = dL_dparams + md.n_mlp_params();
-			// Overwrite vs Accumulate (grid.h:865-867) is handled inside: the owner-computes kernel stores
-			// whole slices, so the reference's full-table memset is only issued for the atomic A/B mode.
-			const GridBackwardMode mode = (GridBackwardMode)g_grid_backward_mode.load();
-			if (lds_level_budget == 0) lds_level_budget = g_default_lds_slice_bytes;
-			// level groups: only where a level's treatment does not depend on its index among ALL levels (every level switched on,
-			// no per-level random stream) and nothing else rides on the pass
-			const uint32_t L = grid.n_levels, F = grid.n_feat;
-			uint32_t n_groups = groups ? std::min(std::max(groups->n_groups, 1u), L) : 1u;
-			if (grid.max_level < 1.0f || io.max_level || grid.stochastic != 0u) n_groups = 1;
-			const std::vector<std::pair<uint32_t, uint32_t>> level_ranges = split_levels(grid, n_groups);
-			// one workspace for all groups: the largest any of them asks for (a group of later levels can bucket levels that the plan of
-			// the whole grid, which takes the first MAX_BUCKET_LEVELS eligible ones, left to the other kinds)
-			GridBackwardWorkspace ws = grid_backward_workspace_size(grid, n, mode, lds_level_budget);
-			if (level_ranges.size() > 1) {
-				ws = GridBackwardWorkspace();
-				for (const auto& r : level_ranges) {
-					const GridBackwardWorkspace w = grid_backward_workspace_size(grid_levels(grid, r.first, r.second), n, mode, lds_level_budget);
-					ws.scratch_bytes = std::max(ws.scratch_bytes, w.scratch_bytes);
-					ws.n_counters = std::max(ws.n_counters, w.n_counters);
-				}
-			}
-			Scratch queues;
-			if (ws.scratch_bytes) {
-				queues = Scratch(stream, ws.scratch_bytes);
-				ws.scratch = queues.ptr;
-				ws.scratch_bytes = queues.bytes;
-				ws.counters = ZeroedCounters::get(stream, ws.n_counters);
-			}
-			PhaseTimer timer = {profiler, stream, /*counts=*/true};
-			ws.phase_hook = grid_backward_phase_hook;  // per-kernel timing when a profiler is attached
-			ws.hook_user = &timer;
-			if (level_ranges.size() <= 1) {
-				grid_backward(stream, grid, io, dL_denc, grid_grads, accumulate, mode, lds_level_budget, ws);
-				if (groups && groups->ready) groups->ready(groups->ctx, md.n_mlp_params(), md.n_mlp_params() + (size_t)grid.offset[L] * F);
-			} else {
-				for (const auto& r : level_ranges) {
-					const uint32_t a = r.first, b = r.second;
-					const GridMeta sub = grid_levels(grid, a, b);
-					timer.counts = a == 0;  // one backward pass per step, however many launches it takes
-					grid_backward(stream, sub, io, dL_denc + (size_t)a * F * stride_k, grid_grads + (size_t)grid.offset[a] * F, accumulate, mode, lds_level_budget, ws);
-					if (groups->ready) groups->ready(groups->ctx, md.n_mlp_params() + (size_t)grid.offset[a] * F, md.n_mlp_params() + (size_t)grid.offset[b] * F);
-				}
-			}
-		}
-		if (dL_dinput) {
-			if (!ctx.dy_dx.ptr) throw std::runtime_error("backward: dL_dinput requested but forward was not run with prepare_input_gradients");
-			grid_backward_input(stream, md.n_input_dims, e.n_output_dims, io, dL_denc, ctx.dy_dx.as<float>(), dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
-		}
+		// max_level as the forward pass of this context saw it
+		const GridSlice s = grid_slice(e, layout, input, n, stride_k, stride_i).max_level(ctx.max_level, ctx.max_level_gpu);
+		if (want_grads) grid_parameter_gradients(stream, timer, s, dL_denc, enc_grads, accumulate, lds_level_budget, groups, md.n_mlp_params());
+		if (dL_dinput) grid_input_gradients(stream, e, layout, s, dL_denc, ctx.dy_dx, dL_dinput);
 	} else if (dL_dinput) {
 		parameterless_backward(stream, e, layout, n, input, dL_denc, stride_k, stride_i, dL_dinput);
 	}
 }
-
-// ---- Encoding<float> (create_encoding(..., Precision::Fp32), cpp_api.cu:165-168): a bare encoding whose parameters, output and gradients are
-// fp32 and which COMPUTES in fp32, as the reference's instantiation does.  Output sample-major [n][padded] (cpp_api.cu:94-95).
-void encoding_forward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const float* params, float* out, ForwardCtx* ctx,
-                                 bool prepare_input_gradients) {
-	check_batch(n, widest_matrix(md));
-	if (n == 0) return;
-	const EncodingDesc& e = md.enc;
-	if (ctx) {
-		ctx->stream = stream;
-		ctx->n = n;
-		ctx->keep_max_level(md.enc);
-	}
-	const uint32_t stride_k = 1u, stride_i = e.padded_output_width;
-	if (e.is_composite()) {
-		composite_forward(stream, e, layout, n, input, params, out, stride_k, stride_i, ctx, prepare_input_gradients);
-	} else if (e.is_grid()) {
-		float* dy_dx = nullptr;
-		if (ctx && prepare_input_gradients) {
-			ctx->dy_dx = Scratch(stream, (size_t)e.n_output_dims * n * md.n_input_dims * sizeof(float));
-			dy_dx = ctx->dy_dx.as<float>();
-		}
-		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
-		io.max_level = e.max_level_gpu;
-		grid_forward_f32(stream, e.grid, io, params, out, dy_dx);
-		const uint32_t n_to_pad = e.padded_output_width - e.n_output_dims;
-		if (n_to_pad > 0) HIP_CHECK(hipMemset2DAsync(out + e.n_output_dims, (size_t)e.padded_output_width * sizeof(float), 0, (size_t)n_to_pad * sizeof(float), n, stream));
-	} else {
-		parameterless_forward(stream, e, layout, n, input, out, stride_k, stride_i);
-	}
-}
-void encoding_backward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const float* dL_doutput, float* dL_dparams,
-                                  const float* input) {
-	check_batch(n, widest_matrix(md));
-	if (n == 0) return;
-	if (ctx.n != n) throw std::runtime_error("backward: batch size does not match the forward context");
-	const EncodingDesc& e = md.enc;
-	uint32_t stride_k = 1u, stride_i = e.padded_output_width;
-	if (e.is_composite()) {
-		Scratch dL_dunreduced;
-		const float* dL_denc = composite_backward_input(stream, e, layout, ctx, n, md.n_input_dims, dL_dinput, dL_doutput, stride_k, stride_i, input, dL_dunreduced);
-		for (const EncodingDesc& g : e.nested) {
-			if (!dL_dparams || !g.is_grid() || g.n_params == 0) continue;
-			GridIO io = {input + (size_t)g.dims_to_encode_begin * layout.in_stride_d, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
-			grid_backward_f32(stream, g.grid, io, dL_denc + (size_t)g.output_row * stride_k, dL_dparams + g.param_offset, /*accumulate=*/false);
-		}
-	} else if (e.is_grid()) {
-		GridIO io = {input, layout.in_stride_i, layout.in_stride_d, n, stride_k, stride_i};
-		io.max_level = ctx.max_level_gpu;  // max_level as the forward pass of this context saw it
-		GridMeta grid = e.grid;
-		grid.max_level = ctx.max_level;
-		if (dL_dparams && e.n_params > 0) grid_backward_f32(stream, grid, io, dL_doutput, dL_dparams, /*accumulate=*/false);  // GradientMode::Overwrite, cpp_api.cu:115
-		if (dL_dinput) {
-			if (!ctx.dy_dx.ptr) throw std::runtime_error("backward: dL_dinput requested but forward was not run with prepare_input_gradients");
-			grid_backward_input_f32(stream, md.n_input_dims, e.n_output_dims, io, dL_doutput, ctx.dy_dx.as<float>(), dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
-		}
-	} else if (dL_dinput) {
-		parameterless_backward(stream, e, layout, n, input, dL_doutput, stride_k, stride_i, dL_dinput);
-	}
-}
+TCNN_INSTANTIATE_VALUE_TYPES(encoding_backward)
 
 }  // namespace tcnn_hip

@@ -8,7 +8,6 @@ namespace tcnn_hip {
 // Process-wide A/B switches (defined, and set through the C ABI, in api_switches.hip).
 // grid backward formulation (GridBackwardMode); TCNN_GRID_BACKWARD=sliced_f32|sliced_f16|atomic|bucketed overrides the default
 extern std::atomic<int> g_grid_backward_mode;
-constexpr uint32_t g_default_lds_slice_bytes = 0u;  // LDS bytes per table slice of the grid backward: 0 = the kernels' default (tcnn_trainer_set_lds_level_budget overrides)
 // Single-kernel network passes (process-wide; tcnn_set_fused_network_passes(0) turns them off):
 //   * training_step: encoding forward, ONE kernel for the network's forward + loss + backward, encoding backward;
 //   * forward() + backward() (Trainer and modules): the forward pass saves only the encoded input; the backward pass runs the same

@@ -81,6 +81,11 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 constexpr bool HALF_IS_BF16 = false;
 #endif
+// A launcher declared `template <typename T>` over the value type of an encoding (half_t or float) is defined in one .hip file, which
+// instantiates it for both behind its definition
+#define TCNN_INSTANTIATE_VALUE_TYPES(launcher) \
+	template decltype(launcher<half_t>) launcher<half_t>; \
+	template decltype(launcher<float>) launcher<float>;
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
