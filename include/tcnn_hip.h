@@ -82,6 +82,25 @@ int tcnn_create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_ou
                                             const char* network_json, tcnn_module_t** out);
 int tcnn_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json, tcnn_module_t** out);
 int tcnn_create_encoding(uint32_t n_input_dims, const char* encoding_json, int requested_precision, tcnn_module_t** out);
+/* The two network factories with create_encoding's `requested_precision`.  The library's own 16-bit precision (tcnn_preferred_precision())
+ * returns exactly what the factories above return.  TCNN_PRECISION_FP32 makes an fp32 network: weights, activations, outputs, dL_dinput and
+ * weight gradients are float and every product runs on the fp32 MFMA (csrc/mlp_general_f32.hip) -- what the reference built without half
+ * precision makes of every network (network_precision_t = float, network.cu:51-138), here a per-module choice.  Such a network is the
+ * layer-by-layer one under every `otype` spelling and reports "otype": "CutlassMLP": hidden widths that are multiples of 16 up to 1024,
+ * input widths (the padded encoding) multiples of 16 up to 1024, up to 1024 padded outputs, any depth >= 1 hidden layer, all ten hidden
+ * activations, the eight output activations of the 16-bit networks -- with the 16-bit CutlassMLP's refusals and texts.  The parameter layout is
+ * the 16-bit network's element for element, and tcnn_module_initialize_params writes the fp32 values the 16-bit network rounds its own from.
+ * The input encoding runs its fp32 path (every encoding of this build, Composite included) and hands the network an fp32 matrix.
+ * param_precision() / output_precision() report TCNN_PRECISION_FP32 (tcnn_default_loss_scale: 1), every `void*` of inference / forward /
+ * backward carries float, tcnn_module_supports_half_input answers 0, backward_backward_input stays "not implemented" as for every network,
+ * and the max_level entries work where the encoding is a lone grid.
+ * Out of scope, TCNN_ERROR_UNSUPPORTED: an fp32 TRAINER -- tcnn_create_from_config_precision(..., TCNN_PRECISION_FP32) refuses by name (the
+ * fused loss and optimizer launches are 16-bit), and with it training_step and the data-parallel entry points, which take trainable models
+ * only.  With the library's own precision it is tcnn_create_from_config. */
+int tcnn_create_network_with_input_encoding_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json,
+                                                      const char* network_json, int requested_precision, tcnn_module_t** out);
+int tcnn_create_network_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json, int requested_precision,
+                                  tcnn_module_t** out);
 void tcnn_module_destroy(tcnn_module_t* m);
 
 /* ---- tcnn::cpp::Module methods, cpp_api.h:96-114 -------------------------------------------------- */
@@ -233,6 +252,19 @@ int tcnn_trainer_training_step_matrices(tcnn_trainable_model_t* tm, tcnn_stream_
                                         int gradient_mode, const tcnn_matrix_t* external_dL_dy, tcnn_train_context_t** ctx_out);
 int tcnn_network_inference_matrices(tcnn_trainable_model_t* tm, tcnn_stream_t stream, const tcnn_matrix_t* input, const tcnn_matrix_t* output,
                                     int use_inference_params);
+/* Network::inference of a MODULE with a network (16-bit or fp32): `input` dense fp32 [n_elements][n_input_dims] as in tcnn_module_inference,
+ * `output` the caller's fp32 matrix of n_output_dims (UNPADDED) x n_elements in either layout with any stride; nothing outside those elements
+ * is written.  An fp32 network stores its values as they are, a 16-bit one its 16-bit results widened.  Bare encodings: TCNN_ERROR_UNSUPPORTED. */
+int tcnn_module_inference_matrix(tcnn_module_t* m, tcnn_stream_t stream, uint32_t n_elements, const float* input, const tcnn_matrix_t* output,
+                                 const void* params);
+/* tcnn_module_backward with the GradientMode spelled out (TCNN_GRADIENT_*): dL_dparams is left alone, overwritten (what tcnn_module_backward
+ * does) or accumulated into.  Every module that tcnn_module_backward takes. */
+int tcnn_module_backward_gradient_mode(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_context_t* ctx, uint32_t n_elements, float* dL_dinput,
+                                       const void* dL_doutput, void* dL_dparams, const float* input, const void* output, const void* params,
+                                       int gradient_mode);
+/* tcnn_create_from_config with a requested precision: the library's own 16-bit precision only (see tcnn_create_network_precision). */
+int tcnn_create_from_config_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* config_json, uint32_t seed,
+                                      int requested_precision, tcnn_trainable_model_t** out);
 /* Trainer::forward / Trainer::backward (trainer.h:97-148) the same way: `input` and `dL_dinput` of either layout. */
 int tcnn_trainer_forward_matrices(tcnn_trainable_model_t* tm, tcnn_stream_t stream, float loss_scale, const tcnn_matrix_t* input, const tcnn_matrix_t* target,
                                   const tcnn_matrix_t* data_pdf, int use_inference_params, int prepare_input_gradients, const tcnn_matrix_t* external_dL_dy,

@@ -172,14 +172,19 @@ private:
 };
 
 // cpp_api.h:121-123 (the caller owns the result, as in the reference)
-inline Module* create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const json& encoding, const json& network) {
+// requested_precision: Precision::Fp32 makes an fp32 network (CutlassMLP under every spelling; parameters, outputs and gradients are float,
+// the encoding runs its fp32 path); the default is the library's own 16-bit precision, i.e. what these factories have always returned
+inline int network_precision_code(Precision p) { return p == Precision::Fp32 ? TCNN_PRECISION_FP32 : tcnn_preferred_precision(); }
+inline Module* create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const json& encoding, const json& network,
+                                                  Precision requested_precision = preferred_precision()) {
 	tcnn_module_t* m = nullptr;
-	check(tcnn_create_network_with_input_encoding(n_input_dims, n_output_dims, json_text(encoding).c_str(), json_text(network).c_str(), &m));
+	check(tcnn_create_network_with_input_encoding_precision(n_input_dims, n_output_dims, json_text(encoding).c_str(), json_text(network).c_str(),
+	                                                        network_precision_code(requested_precision), &m));
 	return new HipModule(m);
 }
-inline Module* create_network(uint32_t n_input_dims, uint32_t n_output_dims, const json& network) {
+inline Module* create_network(uint32_t n_input_dims, uint32_t n_output_dims, const json& network, Precision requested_precision = preferred_precision()) {
 	tcnn_module_t* m = nullptr;
-	check(tcnn_create_network(n_input_dims, n_output_dims, json_text(network).c_str(), &m));
+	check(tcnn_create_network_precision(n_input_dims, n_output_dims, json_text(network).c_str(), network_precision_code(requested_precision), &m));
 	return new HipModule(m);
 }
 inline Module* create_encoding(uint32_t n_input_dims, const json& encoding, Precision requested_precision) {

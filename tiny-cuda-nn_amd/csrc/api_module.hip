@@ -21,6 +21,9 @@ struct tcnn_module {
 	// into that type's range by the largest power of two <= FP32_GRADIENT_SCALE that keeps max |dL_doutput| * scale <=
 	// FP32_GRADIENT_TARGET (found on the device per call) and the results scaled back, exactly.
 	bool fp32_io = false;
+	// tcnn_create_network[_with_input_encoding]_precision(..., TCNN_PRECISION_FP32): the network is the fp32 layer-by-layer one
+	// (NetworkDesc::fp32, mlp_general_f32.h) behind the encoding's fp32 path; fp32_io is set as well (precisions, no 16-bit inputs)
+	bool fp32_network() const { return fp32_io && md.has_network; }
 };
 static constexpr float FP32_GRADIENT_SCALE = 1024.0f, FP32_GRADIENT_TARGET = 16384.0f;
 // the 16-bit copies an fp32 module works on with tcnn_set_fp32_second_order(1)
@@ -60,6 +63,40 @@ int tcnn_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const cha
 	return tcnn_create_network_with_input_encoding(n_input_dims, n_output_dims, "{\"otype\": \"Identity\"}", network_json, out);  // cpp_api.cu:160-162
 }
 
+// The two creators above with create_encoding's `requested_precision`: the library's own 16-bit precision gives exactly their modules;
+// TCNN_PRECISION_FP32 an fp32 network (CutlassMLP under every spelling: the reference without half precision, network.cu:51-138) behind the
+// encoding's fp32 path.
+int tcnn_create_network_with_input_encoding_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* encoding_json, const char* network_json,
+                                                      int requested_precision, tcnn_module_t** out) {
+	if (requested_precision == NATIVE_PRECISION) return tcnn_create_network_with_input_encoding(n_input_dims, n_output_dims, encoding_json, network_json, out);
+	TCNN_API_BEGIN
+	if (requested_precision != TCNN_PRECISION_FP32) {
+		set_last_error(HALF_IS_BF16 ? "create_network: this build (libtcnn_hip_bf16.so) provides bf16 and fp32 networks" : "create_network: this build provides fp16 and fp32 networks");
+		return TCNN_ERROR_UNSUPPORTED;
+	}
+	auto m = std::make_unique<tcnn_module>();
+	m->fp32_io = true;
+	m->md = make_nwie(n_input_dims, n_output_dims, Json::parse(encoding_json), Json::parse(network_json), /*fp32_network=*/true);
+	m->name = m->md.name();
+	*out = m.release();
+	TCNN_API_END
+}
+
+int tcnn_create_network_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json, int requested_precision, tcnn_module_t** out) {
+	return tcnn_create_network_with_input_encoding_precision(n_input_dims, n_output_dims, "{\"otype\": \"Identity\"}", network_json, requested_precision, out);
+}
+
+// create_from_config with a requested precision: the trainer is 16-bit only (its fused loss and optimizer launches have no fp32 path)
+int tcnn_create_from_config_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* config_json, uint32_t seed, int requested_precision,
+                                      tcnn_trainable_model_t** out) {
+	if (requested_precision == NATIVE_PRECISION) return tcnn_create_from_config(n_input_dims, n_output_dims, config_json, seed, out);
+	set_last_error(requested_precision == TCNN_PRECISION_FP32
+	                   ? "create_from_config: the trainer (tcnn_create_from_config, training_step and the data-parallel entry points on it) is 16-bit only in this build; "
+	                     "fp32 networks are modules (tcnn_create_network_precision / tcnn_create_network_with_input_encoding_precision)"
+	                   : "create_from_config: this build's trainer runs in the library's own 16-bit precision only");
+	return TCNN_ERROR_UNSUPPORTED;
+}
+
 int tcnn_create_encoding(uint32_t n_input_dims, const char* encoding_json, int requested_precision, tcnn_module_t** out) {
 	TCNN_API_BEGIN
 	if (requested_precision != NATIVE_PRECISION && requested_precision != TCNN_PRECISION_FP32) {
@@ -83,6 +120,10 @@ void tcnn_module_destroy(tcnn_module_t* m) { delete m; }
 int tcnn_module_inference(tcnn_module_t* m, tcnn_stream_t stream_, uint32_t n, const float* input, void* output, void* params) {
 	TCNN_API_BEGIN
 	hipStream_t stream = (hipStream_t)stream_;
+	if (m->fp32_network()) {
+		model_forward_f32(stream, m->md, IoLayout::dense(m->md), n, input, (float*)output, (const float*)params, nullptr, false);
+		return TCNN_OK;
+	}
 	if (m->fp32_io) {
 		if (begin_pass(stream, m->md, n)) encoding_forward(stream, nullptr, m->md, IoLayout::dense(m->md), n, input, (const float*)params, (float*)output, 1u, m->md.enc.padded_output_width);
 		return TCNN_OK;
@@ -96,7 +137,9 @@ int tcnn_module_forward(tcnn_module_t* m, tcnn_stream_t stream_, uint32_t n, con
 	TCNN_API_BEGIN
 	hipStream_t stream = (hipStream_t)stream_;
 	auto c = std::make_unique<tcnn_context>();
-	if (m->fp32_io) {
+	if (m->fp32_network()) {
+		model_forward_f32(stream, m->md, IoLayout::dense(m->md), n, input, (float*)output, (const float*)params, &c->ctx, prepare_input_gradients != 0);
+	} else if (m->fp32_io) {
 		if (begin_pass(stream, m->md, n, &c->ctx)) {
 			encoding_forward(stream, nullptr, m->md, IoLayout::dense(m->md), n, input, (const float*)params, (float*)output, 1u, m->md.enc.padded_output_width, &c->ctx,
 			                 prepare_input_gradients != 0);
@@ -108,23 +151,59 @@ int tcnn_module_forward(tcnn_module_t* m, tcnn_stream_t stream_, uint32_t n, con
 	TCNN_API_END
 }
 
-int tcnn_module_backward(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_context_t* ctx, uint32_t n, float* dL_dinput, const void* dL_doutput,
-                         void* dL_dparams, const float* input, const void* output, const void* params) {
-	(void)output;
+// backward with the gradient mode spelled out (GradientMode, common.h:152-156): dL_dparams is overwritten, accumulated into, or left alone
+int tcnn_module_backward_gradient_mode(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_context_t* ctx, uint32_t n, float* dL_dinput, const void* dL_doutput,
+                                       void* dL_dparams, const float* input, const void* output, const void* params, int gradient_mode) {
 	TCNN_API_BEGIN
+	if (!m) throw std::runtime_error("backward: null module");
 	if (!ctx) throw std::runtime_error("backward: missing forward context");
+	if (gradient_mode != TCNN_GRADIENT_IGNORE && gradient_mode != TCNN_GRADIENT_OVERWRITE && gradient_mode != TCNN_GRADIENT_ACCUMULATE) throw std::runtime_error("backward: invalid gradient mode");
 	if (ctx->ctx.half_input) throw std::runtime_error("backward: this context was made by tcnn_module_forward_half_input; its backward pass is tcnn_module_backward_half_input");
-	if (m->fp32_io) {  // bare encodings only: neither `output` nor the parameters are needed by their first-order backward pass
-		(void)params;
+	if (!dL_dparams) gradient_mode = TCNN_GRADIENT_IGNORE;
+	if (m->fp32_network()) {
+		model_backward_f32((hipStream_t)stream, m->md, IoLayout::dense(m->md), ctx->ctx, n, dL_dinput, (const float*)dL_doutput, (float*)dL_dparams, input, (const float*)output,
+		                   (const float*)params, gradient_mode);
+		return TCNN_OK;
+	}
+	if (m->fp32_io) {  // bare encodings: neither `output` nor the parameters are needed by their first-order backward pass
 		if (begin_backward(m->md, ctx->ctx, n)) {
 			encoding_backward((hipStream_t)stream, nullptr, m->md, IoLayout::dense(m->md), ctx->ctx, n, dL_dinput, (const float*)dL_doutput, 1u, m->md.enc.padded_output_width,
-			                  (float*)dL_dparams, dL_dparams != nullptr, /*accumulate=*/false, input);  // GradientMode::Overwrite, cpp_api.cu:115
+			                  (float*)dL_dparams, gradient_mode != TCNN_GRADIENT_IGNORE, gradient_mode == TCNN_GRADIENT_ACCUMULATE, input);
 		}
 		return TCNN_OK;
 	}
 	model_backward((hipStream_t)stream, nullptr, m->md, IoLayout::dense(m->md), ctx->ctx, n, dL_dinput, (const half_t*)dL_doutput, (half_t*)dL_dparams, input, (const half_t*)output,
-	               (const half_t*)params,
-	               dL_dparams ? TCNN_GRADIENT_OVERWRITE : TCNN_GRADIENT_IGNORE, m->lds_level_budget);  // cpp_api.cu:115
+	               (const half_t*)params, gradient_mode, m->lds_level_budget);
+	TCNN_API_END
+}
+
+int tcnn_module_backward(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_context_t* ctx, uint32_t n, float* dL_dinput, const void* dL_doutput,
+                         void* dL_dparams, const float* input, const void* output, const void* params) {
+	return tcnn_module_backward_gradient_mode(m, stream, ctx, n, dL_dinput, dL_doutput, dL_dparams, input, output, params, TCNN_GRADIENT_OVERWRITE);  // cpp_api.cu:115
+}
+
+// network->inference of a module (object.h:214-271): into the caller's fp32 matrix of n_output_dims (unpadded) x n, either layout
+int tcnn_module_inference_matrix(tcnn_module_t* m, tcnn_stream_t stream_, uint32_t n, const float* input, const tcnn_matrix_t* output, const void* params) {
+	TCNN_API_BEGIN
+	if (!m || !output) throw std::runtime_error("tcnn_module_inference_matrix: null argument");
+	if (!m->md.has_network) {
+		set_last_error(std::string("inference_matrix: ") + m->md.enc.name() + " is a bare encoding; its inference is tcnn_module_inference");
+		return TCNN_ERROR_UNSUPPORTED;
+	}
+	const uint32_t width = m->md.output_width();
+	if (output->m != width || output->n != n || !output->data) throw std::runtime_error("inference_matrix: the output matrix must be n_output_dims x n_elements");
+	const bool cm = output->layout == TCNN_LAYOUT_COLUMN_MAJOR;
+	if (!cm && output->layout != TCNN_LAYOUT_ROW_MAJOR) throw std::runtime_error("inference_matrix: invalid layout");
+	if (output->stride < (cm ? width : n)) throw std::runtime_error("inference_matrix: the stride is below the leading dimension");
+	const uint32_t stride_i = cm ? output->stride : 1u, stride_j = cm ? 1u : output->stride;
+	hipStream_t stream = (hipStream_t)stream_;
+	if (m->fp32_network()) {
+		const MlpF32Output trimmed = {(float*)output->data, width, stride_i, stride_j};
+		model_forward_f32(stream, m->md, IoLayout::dense(m->md), n, input, nullptr, (const float*)params, nullptr, false, &trimmed);
+		return TCNN_OK;
+	}
+	check_batch(n, widest_matrix(m->md));
+	inference_to_f32(stream, m->md, IoLayout::dense(m->md), n, input, (const half_t*)params, (float*)output->data, stride_i, stride_j);
 	TCNN_API_END
 }
 

@@ -63,6 +63,9 @@ struct NetworkDesc {
 	uint32_t n_output_dims = 0;
 	uint32_t n_hidden_layers = 0;
 	std::string otype;
+	// weights, activations and gradients are float and the network is the fp32 layer-by-layer one (mlp_general_f32.h) under every `otype`
+	// spelling: what the reference built without half precision makes of every network (network.cu:51-138 with network_precision_t = float)
+	bool fp32 = false;
 	Json hyperparams() const;  // fully_fused_mlp.h:139-147
 };
 
@@ -93,7 +96,7 @@ struct Model {
 };
 
 EncodingDesc create_encoding_desc(uint32_t n_dims, const Json& enc, uint32_t alignment);  // encoding.cu:131-145
-Model make_nwie(uint32_t n_input_dims, uint32_t n_output_dims, const Json& encoding, const Json& network);
+Model make_nwie(uint32_t n_input_dims, uint32_t n_output_dims, const Json& encoding, const Json& network, bool fp32_network = false);
 const char* loss_name(LossType loss);  // loss.cu:57-65
 LossType string_to_loss(const std::string& s);
 void parse_adam(AdamHyper& h, const Json& p);  // adam.h:221-281

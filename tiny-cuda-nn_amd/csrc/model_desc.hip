@@ -385,7 +385,7 @@ EncodingDesc create_encoding_desc(uint32_t n_dims, const Json& enc, uint32_t ali
 
 Json NetworkDesc::hyperparams() const {
 	Json j = Json::object();
-	j["otype"] = mlp_layer_by_layer(mlp) ? "CutlassMLP" : "FullyFusedMLP";  // cutlass_mlp.h:152, fully_fused_mlp.h:141
+	j["otype"] = fp32 || mlp_layer_by_layer(mlp) ? "CutlassMLP" : "FullyFusedMLP";  // cutlass_mlp.h:152, fully_fused_mlp.h:141
 	j["activation"] = to_string((Activation)mlp.activation);
 	j["output_activation"] = to_string((Activation)mlp.output_activation);
 	j["n_neurons"] = mlp.width;
@@ -393,18 +393,21 @@ Json NetworkDesc::hyperparams() const {
 	return j;
 }
 
-static NetworkDesc create_network_desc(uint32_t n_input_dims, uint32_t n_output_dims, const Json& net) {  // network.cu:51-138
+// fp32: the fp32 layer-by-layer network whatever the spelling (the reference without half precision: every network is a CutlassMLP) -- no
+// fused width is special, the limits and their texts are the layer-by-layer network's
+static NetworkDesc create_network_desc(uint32_t n_input_dims, uint32_t n_output_dims, const Json& net, bool fp32) {  // network.cu:51-138
 	const std::string otype = net.value("otype", "MLP");
 	const bool known = equals_case_insensitive(otype, "MegakernelMLP") || equals_case_insensitive(otype, "FullyFusedMLP") ||
 	                   equals_case_insensitive(otype, "MLP") || equals_case_insensitive(otype, "CutlassMLP");
 	if (!known) throw std::runtime_error("Invalid network type: " + otype);
 	NetworkDesc d;
 	d.otype = otype;
+	d.fp32 = fp32;
 	const uint32_t n_neurons = net.value("n_neurons", 128u);
 	// network.cu:51-77, 129-137: FullyFusedMLP exists for four widths; "MLP" / "CutlassMLP" take those where they can and the
 	// layer-by-layer network (mlp_general.hip) for every other multiple of 16
-	const bool fused_width = mlp_fused_width(n_neurons);
-	const bool wants_fused = equals_case_insensitive(otype, "MegakernelMLP") || equals_case_insensitive(otype, "FullyFusedMLP");
+	const bool fused_width = !fp32 && mlp_fused_width(n_neurons);
+	const bool wants_fused = !fp32 && (equals_case_insensitive(otype, "MegakernelMLP") || equals_case_insensitive(otype, "FullyFusedMLP"));
 	if (!fused_width && wants_fused) {
 		throw std::runtime_error("FullyFusedMLP only supports 16, 32, 64, and 128 neurons, but got " + std::to_string(n_neurons) +
 		                         ". Use CutlassMLP instead.");
@@ -433,7 +436,7 @@ static NetworkDesc create_network_desc(uint32_t n_input_dims, uint32_t n_output_
 	d.mlp.width = n_neurons;
 	d.mlp.activation = (uint32_t)act;
 	d.mlp.padded_out = next_multiple(n_output_dims, 16u);  // fully_fused_mlp.cu:656
-	const bool fused = !mlp_layer_by_layer(d.mlp);
+	const bool fused = !fp32 && !mlp_layer_by_layer(d.mlp);
 	const char* const name = fused ? "FullyFusedMLP" : "CutlassMLP";
 	d.n_hidden_layers = net.value("n_hidden_layers", 5u);
 	if (d.n_hidden_layers == 0) throw std::runtime_error(std::string(name) + " requires at least 1 hidden layer (3 layers in total).");
@@ -507,12 +510,12 @@ void Model::initialize_params(hipStream_t stream, Pcg32& rng, float* params_full
 	}
 }
 
-Model make_nwie(uint32_t n_input_dims, uint32_t n_output_dims, const Json& encoding, const Json& network) {
+Model make_nwie(uint32_t n_input_dims, uint32_t n_output_dims, const Json& encoding, const Json& network, bool fp32_network) {
 	Model md;
 	md.n_input_dims = n_input_dims;
 	md.enc = create_encoding_desc(n_input_dims, encoding, /*minimum_alignment(network)=*/16);  // network.cu:79-98 -> 16
 	md.has_network = true;
-	md.net = create_network_desc(md.enc.padded_output_width, n_output_dims, network);
+	md.net = create_network_desc(md.enc.padded_output_width, n_output_dims, network, fp32_network);
 	md.finish();
 	return md;
 }

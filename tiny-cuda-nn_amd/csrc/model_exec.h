@@ -115,6 +115,14 @@ void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, cons
 void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const half_t* dL_doutput,
                     half_t* dL_dparams, const float* input, const half_t* output, const half_t* params, int gradient_mode,
                     uint32_t lds_level_budget, half_t* dL_dinput16 = nullptr);  // dL_dinput16: of a context made with input16, instead of dL_dinput
+// The same two passes of a model whose network is the fp32 one (NetworkDesc::fp32, mlp_general_f32.h): parameters, output, dL_doutput and
+// dL_dparams are float, the encoding runs its fp32 path (encoding_forward<float> / encoding_backward<float>) and hands the network an fp32
+// feature-major matrix; the context keeps that matrix and the saved fp32 activations.  trimmed (inference only, ctx == nullptr): the result
+// goes to the caller's trimmed matrix instead of `output`.
+void model_forward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, float* output, const float* params, ForwardCtx* ctx,
+                       bool prepare_input_gradients, const MlpF32Output* trimmed = nullptr);
+void model_backward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const float* dL_doutput, float* dL_dparams,
+                        const float* input, const float* output, const float* params, int gradient_mode);
 // network->inference into the caller's fp32 matrix (object.h:214-271)
 void inference_to_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const half_t* params, float* out, uint32_t stride_i, uint32_t stride_j);
 

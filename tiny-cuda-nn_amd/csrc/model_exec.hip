@@ -5,6 +5,7 @@
 
 #include "half_input_kernels.h"
 #include "host_common.h"
+#include "mlp_general_f32.h"
 #include "switches.h"
 
 namespace tcnn_hip {
@@ -19,6 +20,7 @@ int refuse_max_level(const Model& md) {
 std::string half_input_refusal(const Model& md) {
 	const EncodingDesc& e = md.enc;
 	const std::string prefix = std::string("half_input: ") + e.name();
+	if (md.has_network && md.net.fp32) return "half_input: an fp32 network reads fp32 inputs: 16-bit inputs go to the 16-bit modules tcnn_create_network makes";
 	if (!md.has_network) return prefix + " is a bare encoding: 16-bit inputs go to the modules tcnn_create_network makes (positions need fp32)";
 	if (e.kind != EncodingKind::Identity) return prefix + " in front of the network reads fp32 inputs: 16-bit inputs go to the modules tcnn_create_network makes";
 	if (e.id_scale != 1.0f || e.id_offset != 0.0f) return prefix + " with a scale other than 1 or an offset other than 0 is not exact on 16-bit values";
@@ -355,6 +357,55 @@ void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, con
 	}
 
 	encoding_share(dL_denc, stride_k, stride_i);
+}
+
+// ---- the fp32 network (mlp_general_f32.h) behind the encoding's fp32 path --------------------------------------------------------------
+void model_forward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, float* output, const float* params, ForwardCtx* ctx,
+                       bool prepare_input_gradients, const MlpF32Output* trimmed) {
+	if (!md.has_network || !md.net.fp32) throw std::runtime_error("model_forward_f32: not an fp32 network");
+	if (trimmed && ctx) throw std::runtime_error("model_forward_f32: the trimmed output is for inference");
+	if (ctx) ctx->half_input = false;
+	if (!begin_pass(stream, md, n, ctx)) return;
+	Scratch enc_local;
+	Scratch& enc = ctx ? ctx->enc : enc_local;
+	enc = Scratch(stream, (size_t)md.enc.padded_output_width * n * sizeof(float));
+	encoding_forward(stream, nullptr, md, layout, n, input, params + md.n_mlp_params(), enc.as<float>(), n, 1u, ctx, prepare_input_gradients);
+	float* hidden = nullptr;
+	if (ctx) {
+		ctx->hidden = Scratch(stream, mlp_f32_saved_activation_bytes(md.net.mlp, n));
+		hidden = ctx->hidden.as<float>();
+	}
+	mlp_f32_forward(stream, md.net.mlp, n, params, enc.as<float>(), hidden, trimmed ? nullptr : output, trimmed ? *trimmed : MlpF32Output());
+}
+
+void model_backward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const float* dL_doutput, float* dL_dparams,
+                        const float* input, const float* output, const float* params, int gradient_mode) {
+	if (!md.has_network || !md.net.fp32) throw std::runtime_error("model_backward_f32: not an fp32 network");
+	if (!begin_backward(md, ctx, n)) return;
+	if (!ctx.enc.ptr || !ctx.hidden.ptr) throw std::runtime_error("backward: this context holds no saved activations of an fp32 network");
+	const bool want_grads = gradient_mode != TCNN_GRADIENT_IGNORE && dL_dparams != nullptr;
+	const bool accumulate = gradient_mode == TCNN_GRADIENT_ACCUMULATE;
+	if (!want_grads && !dL_dinput) return;
+	const EncodingDesc& e = md.enc;
+	const MlpMeta& mlp = md.net.mlp;
+	const bool need_denc = (want_grads && e.n_params > 0) || dL_dinput;
+	Scratch params_t(stream, md.n_mlp_params() * sizeof(float));
+	mlp_f32_transpose_weights(stream, mlp, params, params_t.as<float>());
+	const uint32_t n_partials = mlp_f32_n_partials(mlp, n);
+	Scratch partials, denc, dpre;
+	if (want_grads) partials = Scratch(stream, (size_t)n_partials * md.n_mlp_params() * sizeof(float));
+	if (need_denc) denc = Scratch(stream, (size_t)e.padded_output_width * n * sizeof(float));
+	if (mlp.output_activation != (uint32_t)Activation::None) {  // continue from dL/d(pre-activation) (fully_fused_mlp.cu:760-763)
+		if (!output) throw std::runtime_error("backward: the network output is required when an output activation is set");
+		dpre = Scratch(stream, (size_t)mlp.padded_out * n * sizeof(float));
+		mlp_f32_output_activation_backward(stream, mlp, n, output, dL_doutput, dpre.as<float>());
+		dL_doutput = dpre.as<float>();
+	}
+	Scratch workspace(stream, mlp_f32_backward_workspace_bytes(mlp, n));
+	mlp_f32_backward(stream, mlp, n, params_t.as<float>(), ctx.enc.as<float>(), ctx.hidden.as<float>(), dL_doutput, need_denc ? denc.as<float>() : nullptr,
+	                 want_grads ? partials.as<float>() : nullptr, workspace.ptr);
+	if (want_grads) mlp_f32_finalize_gradients(stream, mlp, n_partials, partials.as<float>(), dL_dparams, accumulate);
+	if (need_denc) encoding_backward(stream, nullptr, md, layout, ctx, n, dL_dinput, (const float*)denc.as<float>(), n, 1u, dL_dparams, want_grads, accumulate, input);
 }
 
 static void grid_backward_phase_hook(void* user, int phase, int begin) {

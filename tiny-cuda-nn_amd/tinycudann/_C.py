@@ -106,6 +106,11 @@ _sig("tcnn_loss_evaluate", _i, C.c_char_p, _vp, C.c_uint32, C.c_uint32, C.c_uint
 _sig("tcnn_create_network_with_input_encoding", _i, _u32, _u32, _cp, _cp, C.POINTER(_vp))
 _sig("tcnn_create_network", _i, _u32, _u32, _cp, C.POINTER(_vp))
 _sig("tcnn_create_encoding", _i, _u32, _cp, _i, C.POINTER(_vp))
+_sig("tcnn_create_network_with_input_encoding_precision", _i, _u32, _u32, _cp, _cp, _i, C.POINTER(_vp))
+_sig("tcnn_create_network_precision", _i, _u32, _u32, _cp, _i, C.POINTER(_vp))
+_sig("tcnn_create_from_config_precision", _i, _u32, _u32, _cp, _u32, _i, C.POINTER(_vp))
+_sig("tcnn_module_inference_matrix", _i, _vp, _vp, _u32, _vp, _vp, _vp)
+_sig("tcnn_module_backward_gradient_mode", _i, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i)
 _sig("tcnn_module_destroy", None, _vp)
 _sig("tcnn_module_inference", _i, _vp, _vp, _u32, _vp, _vp, _vp)
 _sig("tcnn_module_forward", _i, _vp, _vp, _u32, _vp, _vp, _vp, _i, C.POINTER(_vp))
@@ -429,6 +434,10 @@ class _DeviceGuard:
         return False
 
 
+class _Matrix(C.Structure):  # tcnn_matrix_t
+    _fields_ = [("data", C.c_void_p), ("m", C.c_uint32), ("n", C.c_uint32), ("stride", C.c_uint32), ("layout", C.c_int)]
+
+
 class Module:
     """Mirror of the pybind `Module` (bindings.cpp:75-248)."""
 
@@ -519,6 +528,44 @@ class Module:
                 _check(_lib.tcnn_module_backward_backward_input(self._h, _stream(), ctx._h, batch_size, _ptr(dL_ddLdinput), _ptr(input), _ptr(dL_doutput),
                                                                 _ptr(dL_dparams), _ptr(dL_ddLdoutput), _ptr(dL_dinput), _ptr(params)))
             return dL_ddLdoutput, dL_dparams, dL_dinput
+
+    def bwd_into(self, ctx, input, params, output, dL_doutput, dL_dparams, gradient_mode=GradientMode.Accumulate, want_dL_dinput=True):
+        """tcnn_module_backward_gradient_mode: the backward pass with the parameter gradients written into the CALLER'S `dL_dparams`
+        (overwritten or accumulated into; None or GradientMode.Ignore: left alone) -> dL_dinput (fp32 [n][n_input_dims]) or None."""
+        for t in (input, params, output, dL_doutput) + (() if dL_dparams is None else (dL_dparams,)):
+            _check_input(t)
+        param_dtype, out_dtype = TORCH_DTYPE[Precision(self.param_precision())], TORCH_DTYPE[Precision(self.output_precision())]
+        if input.dtype != torch.float32 or params.dtype != param_dtype or output.dtype != out_dtype or dL_doutput.dtype != out_dtype or \
+                (dL_dparams is not None and dL_dparams.dtype != param_dtype):
+            raise RuntimeError("bwd_into: wrong tensor precision")
+        if input.shape[1] != self.n_input_dims() or output.shape != (input.shape[0], self.n_output_dims()) or dL_doutput.shape != output.shape or \
+                params.shape[0] != self.n_params() or (dL_dparams is not None and dL_dparams.shape != params.shape):
+            raise RuntimeError("bwd_into: wrong tensor size")
+        handle = ctx._h if isinstance(ctx, Context) else C.c_void_p(ctx.handle())
+        with _DeviceGuard(input.device):
+            dL_dinput = torch.empty_like(input) if want_dL_dinput else None
+            _check(_lib.tcnn_module_backward_gradient_mode(self._h, _stream(), handle, input.shape[0], _ptr(dL_dinput), _ptr(dL_doutput), _ptr(dL_dparams),
+                                                           _ptr(input), _ptr(output), _ptr(params), int(gradient_mode)))
+        return dL_dinput
+
+    def inference_into(self, input, params, out):
+        """tcnn_module_inference_matrix: the network's inference into the caller's fp32 tensor `out` of shape [n][n_output_dims (UNPADDED)] -- a
+        view with any row stride -- or its transpose, [n_output_dims][n] (the row-major matrix of the C ABI)."""
+        _check_input(input)
+        _check_input(params)
+        if input.dtype != torch.float32 or out.dtype != torch.float32 or not out.is_cuda or out.dim() != 2:
+            raise RuntimeError("inference_into: input and out must be float32 GPU matrices")
+        n = input.shape[0]
+        if out.shape[0] == n and out.stride(1) == 1:
+            layout, dims, stride = 1, out.shape[1], out.stride(0)  # TCNN_LAYOUT_COLUMN_MAJOR: one sample's values contiguous
+        elif out.shape[1] == n and out.stride(1) == 1:
+            layout, dims, stride = 0, out.shape[0], out.stride(0)
+        else:
+            raise RuntimeError("inference_into: out must be [n][dims] or [dims][n] with unit stride along its last dimension")
+        matrix = _Matrix(C.c_void_p(out.data_ptr()), dims, n, stride, layout)
+        with _DeviceGuard(input.device):
+            _check(_lib.tcnn_module_inference_matrix(self._h, _stream(), n, _ptr(input), C.byref(matrix), _ptr(params)))
+        return out
 
     def initial_params(self, seed):  # bindings.cpp:284-289
         out = torch.zeros((self.n_params(),), dtype=torch.float32, device="cuda")
@@ -668,6 +715,8 @@ class ExtModule:
     grid_level_n_params = Module.grid_level_n_params
     grid_level_params_offset = Module.grid_level_params_offset
     nested_layout = Module.nested_layout
+    bwd_into = Module.bwd_into
+    inference_into = Module.inference_into
 
 
 def ext_apply(module, x, params, loss_scale):
@@ -688,6 +737,30 @@ def create_network(n_input_dims, n_output_dims, network):
         return ExtModule(EXT.create_network(n_input_dims, n_output_dims, _dumps(network).decode()))
     h = C.c_void_p()
     _check(_lib.tcnn_create_network(n_input_dims, n_output_dims, _dumps(network), C.byref(h)))
+    return Module(h.value)
+
+
+def _native_or_fp32(precision):
+    return preferred_precision() if precision is None else Precision(int(precision))
+
+
+def create_network_with_input_encoding_precision(n_input_dims, n_output_dims, encoding, network, precision=None):
+    """tcnn_create_network_with_input_encoding_precision: Precision.Fp32 makes an fp32 network behind the encoding's fp32 path; the library's
+    own 16-bit precision (None) exactly what create_network_with_input_encoding makes."""
+    precision = _native_or_fp32(precision)
+    if EXT is not None:
+        return ExtModule(EXT.create_network_with_input_encoding_precision(n_input_dims, n_output_dims, _dumps(encoding).decode(), _dumps(network).decode(), int(precision)))
+    h = C.c_void_p()
+    _check(_lib.tcnn_create_network_with_input_encoding_precision(n_input_dims, n_output_dims, _dumps(encoding), _dumps(network), int(precision), C.byref(h)))
+    return Module(h.value)
+
+
+def create_network_precision(n_input_dims, n_output_dims, network, precision=None):
+    precision = _native_or_fp32(precision)
+    if EXT is not None:
+        return ExtModule(EXT.create_network_precision(n_input_dims, n_output_dims, _dumps(network).decode(), int(precision)))
+    h = C.c_void_p()
+    _check(_lib.tcnn_create_network_precision(n_input_dims, n_output_dims, _dumps(network), int(precision), C.byref(h)))
     return Module(h.value)
 
 

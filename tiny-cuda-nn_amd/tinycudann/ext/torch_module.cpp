@@ -25,6 +25,9 @@ struct Abi {  // include/tcnn_hip.h, the entries this binding calls
 	int (*create_nwie)(uint32_t, uint32_t, const char*, const char*, tcnn_module**) = nullptr;
 	int (*create_network)(uint32_t, uint32_t, const char*, tcnn_module**) = nullptr;
 	int (*create_encoding)(uint32_t, const char*, int, tcnn_module**) = nullptr;
+	// the network factories with a requested precision (fp32 networks)
+	int (*create_nwie_precision)(uint32_t, uint32_t, const char*, const char*, int, tcnn_module**) = nullptr;
+	int (*create_network_precision)(uint32_t, uint32_t, const char*, int, tcnn_module**) = nullptr;
 	void (*module_destroy)(tcnn_module*) = nullptr;
 	int (*inference)(tcnn_module*, void*, uint32_t, const float*, void*, void*) = nullptr;
 	int (*forward)(tcnn_module*, void*, uint32_t, const float*, void*, void*, int, tcnn_context**) = nullptr;
@@ -71,6 +74,8 @@ void bind_library(const std::string& path) {
 	resolve(lib, capi.create_nwie, "tcnn_create_network_with_input_encoding");
 	resolve(lib, capi.create_network, "tcnn_create_network");
 	resolve(lib, capi.create_encoding, "tcnn_create_encoding");
+	resolve(lib, capi.create_nwie_precision, "tcnn_create_network_with_input_encoding_precision");
+	resolve(lib, capi.create_network_precision, "tcnn_create_network_precision");
 	resolve(lib, capi.module_destroy, "tcnn_module_destroy");
 	resolve(lib, capi.inference, "tcnn_module_inference");
 	resolve(lib, capi.forward, "tcnn_module_forward");
@@ -378,6 +383,17 @@ std::shared_ptr<Module> create_network(uint32_t n_input_dims, uint32_t n_output_
 	check(capi.create_network(n_input_dims, n_output_dims, network_json.c_str(), &m));
 	return std::make_shared<Module>(m);
 }
+std::shared_ptr<Module> create_network_with_input_encoding_precision(uint32_t n_input_dims, uint32_t n_output_dims, const std::string& encoding_json,
+                                                                      const std::string& network_json, int precision) {
+	tcnn_module* m = nullptr;
+	check(capi.create_nwie_precision(n_input_dims, n_output_dims, encoding_json.c_str(), network_json.c_str(), precision, &m));
+	return std::make_shared<Module>(m);
+}
+std::shared_ptr<Module> create_network_precision(uint32_t n_input_dims, uint32_t n_output_dims, const std::string& network_json, int precision) {
+	tcnn_module* m = nullptr;
+	check(capi.create_network_precision(n_input_dims, n_output_dims, network_json.c_str(), precision, &m));
+	return std::make_shared<Module>(m);
+}
 std::shared_ptr<Module> create_encoding(uint32_t n_input_dims, const std::string& encoding_json, int precision) {
 	tcnn_module* m = nullptr;
 	check(capi.create_encoding(n_input_dims, encoding_json.c_str(), precision, &m));
@@ -393,7 +409,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 	m.def("library_path", [] { return capi.path; });
 	m.def("batch_size_granularity", [] { return capi.batch_size_granularity(); });
 	m.def("default_loss_scale", [](int precision) { return capi.default_loss_scale(precision); });
-	py::class_<Context, std::shared_ptr<Context>>(m, "Context").def_property_readonly("valid", &Context::valid);
+	py::class_<Context, std::shared_ptr<Context>>(m, "Context")
+		.def_property_readonly("valid", &Context::valid)
+		.def("handle", [](const Context& c) { return (uintptr_t)c.h; });  // for the ctypes helpers of _C.py (bwd_into)
 	py::class_<Module, std::shared_ptr<Module>>(m, "Module")
 		.def("fwd", &Module::fwd)
 		.def("bwd", &Module::bwd)
@@ -415,5 +433,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 	m.def("create_network_with_input_encoding", &create_network_with_input_encoding);
 	m.def("create_network", &create_network);
 	m.def("create_encoding", &create_encoding);
+	m.def("create_network_with_input_encoding_precision", &create_network_with_input_encoding_precision);
+	m.def("create_network_precision", &create_network_precision);
 	m.def("apply", &module_apply, "y = module(x, params) as an autograd node (first and second order), dL/doutput scaled by loss_scale on the way down");
 }

@@ -224,35 +224,56 @@ class Module(torch.nn.Module):
         self.native_tcnn_module.jit_fusion = val
 
 
-class NetworkWithInputEncoding(Module):
-    """Input encoding followed by a fully fused MLP: `[:, n_input_dims]` float -> `[:, n_output_dims]`."""
+def _requested_precision(kind, dtype):
+    """dtype=None: None (the creators without a precision, today's behaviour); otherwise the library's Precision"""
+    if dtype is None:
+        return None
+    if dtype == torch.float32:
+        return _C.Precision.Fp32
+    if dtype == torch.float16:
+        return _C.Precision.Fp16
+    if dtype == torch.bfloat16:  # the bfloat16 build of the library (TCNN_PRECISION=bf16)
+        return _C.Precision.Bf16
+    raise ValueError(f"{kind} only supports fp32, fp16 or bf16 precision, but got {dtype}")
 
-    def __init__(self, n_input_dims, n_output_dims, encoding_config, network_config, seed=1337):
+
+class NetworkWithInputEncoding(Module):
+    """Input encoding followed by a fully fused MLP: `[:, n_input_dims]` float -> `[:, n_output_dims]`.
+    dtype=torch.float32: an fp32 network (CutlassMLP) behind the encoding's fp32 path -- params, outputs and gradients are float32, the
+    loss scale is 1."""
+
+    def __init__(self, n_input_dims, n_output_dims, encoding_config, network_config, seed=1337, dtype=None):
         if not _C.has_networks():
             raise RuntimeError("Cannot create `NetworkWithInputEncoding`: the native library was built without networks.")
         self.n_input_dims = n_input_dims
         self.n_output_dims = n_output_dims
         self.encoding_config = encoding_config
         self.network_config = network_config
+        self.precision = _requested_precision("NetworkWithInputEncoding", dtype)
         super().__init__(seed=seed)
 
     def _native_tcnn_module(self):
-        return _C.create_network_with_input_encoding(self.n_input_dims, self.n_output_dims, self.encoding_config, self.network_config)
+        if self.__dict__.get("precision") is None:
+            return _C.create_network_with_input_encoding(self.n_input_dims, self.n_output_dims, self.encoding_config, self.network_config)
+        return _C.create_network_with_input_encoding_precision(self.n_input_dims, self.n_output_dims, self.encoding_config, self.network_config, self.precision)
 
 
 class Network(Module):
     """Fully fused MLP on raw inputs (identity encoding, inputs padded with ones to a multiple of 16)."""
 
-    def __init__(self, n_input_dims, n_output_dims, network_config, seed=1337):
+    def __init__(self, n_input_dims, n_output_dims, network_config, seed=1337, dtype=None):
         if not _C.has_networks():
             raise RuntimeError("Cannot create `Network`: the native library was built without networks.")
         self.n_input_dims = n_input_dims
         self.n_output_dims = n_output_dims
         self.network_config = network_config
+        self.precision = _requested_precision("Network", dtype)  # torch.float32: an fp32 network (see NetworkWithInputEncoding)
         super().__init__(seed=seed)
 
     def _native_tcnn_module(self):
-        return _C.create_network(self.n_input_dims, self.n_output_dims, self.network_config)
+        if self.__dict__.get("precision") is None:  # (also: a module pickled before `dtype` existed)
+            return _C.create_network(self.n_input_dims, self.n_output_dims, self.network_config)
+        return _C.create_network_precision(self.n_input_dims, self.n_output_dims, self.network_config, self.precision)
 
 
 class Encoding(Module):

@@ -106,6 +106,11 @@ class DataParallel:
     def __init__(self, tm, mode="sharded", loss_scale=128.0, n_buckets=None, level_groups=2, single_rank_ok=False, verify_direct=True):
         if mode not in ("sharded", "allreduce", "pipelined", "pipelined_sharded", "direct"):
             raise ValueError(f"unknown data-parallel mode {mode!r}")
+        if not hasattr(tm, "param_gradients") and callable(getattr(tm, "param_precision", None)):
+            # a module, not a trainable model: the exchange runs on the trainer's 16-bit gradient buffer, and fp32 networks are modules only
+            fp32 = int(tm.param_precision()) == 0
+            raise RuntimeError("DataParallel: data-parallel entry points take a trainable model (create_from_config)"
+                               + (", and the trainer is 16-bit only: an fp32 module is not supported" if fp32 else ""))
         self.tm, self.mode, self.loss_scale, self.n_buckets = tm, mode, loss_scale, n_buckets
         # single_rank_ok: run the collectives even in a process group of ONE rank (tests: the whole exchange on the real backend
         # -- RCCL -- where only one GPU exists; every collective is then the identity)
