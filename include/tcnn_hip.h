@@ -84,7 +84,7 @@ int tcnn_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const cha
 int tcnn_create_encoding(uint32_t n_input_dims, const char* encoding_json, int requested_precision, tcnn_module_t** out);
 /* The two network factories with create_encoding's `requested_precision`.  The library's own 16-bit precision (tcnn_preferred_precision())
  * returns exactly what the factories above return.  TCNN_PRECISION_FP32 makes an fp32 network: weights, activations, outputs, dL_dinput and
- * weight gradients are float and every product runs on the fp32 MFMA (csrc/mlp_general_f32.hip) -- what the reference built without half
+ * weight gradients are float and every product runs on the fp32 MFMA (csrc/mlp_general_fp32.hip) -- what the reference built without half
  * precision makes of every network (network_precision_t = float, network.cu:51-138), here a per-module choice.  Such a network is the
  * layer-by-layer one under every `otype` spelling and reports "otype": "CutlassMLP": hidden widths that are multiples of 16 up to 1024,
  * input widths (the padded encoding) multiples of 16 up to 1024, up to 1024 padded outputs, any depth >= 1 hidden layer, all ten hidden

@@ -1,4 +1,4 @@
-"""Times the fp32 network (csrc/mlp_general_f32.hip, tcnn_create_network_precision with TCNN_PRECISION_FP32) against the 16-bit network the
+"""Times the fp32 network (csrc/mlp_general_fp32.hip, tcnn_create_network_precision with TCNN_PRECISION_FP32) against the 16-bit network the
 library makes of the same shape, through the module entry points (no trainer: fp32 networks are modules): forward + backward (dL/dinput
 and parameter gradients) and inference of 64 -> 64 x 2 -> 16 and 32 -> 256 x 4 -> 16 at N = 2^18.
 

@@ -97,6 +97,9 @@ def _load(keep, bf16):
         build()
         _libs[key] = C.CDLL(_VARIANTS[key][0])
         assert _libs[key].emuzr_keeps_zero_records() == int(key[0])
+        if not key[0]:  # (the fp32 network's entry points that do not return int: emu_mlp_f32.py)
+            _libs[key].emuf32_saved_activation_floats.restype = C.c_uint64
+            _libs[key].emuf32_n_partials.restype = C.c_uint32
     return _libs[key]
 
 

@@ -1,7 +1,9 @@
 // emu_driver_mlp.cpp -- the network's part of the emulator's driver (emu_driver.h): the launchers of csrc/mlp_kernels.hip (which brings
-// csrc/mlp_general.hip along) and the register-resident kernels they choose between, as one unit.  TEST INFRASTRUCTURE ONLY -- see hip_emu.h.
+// csrc/mlp_general.hip along, the 16-bit layer-by-layer network), its fp32 twin csrc/mlp_general_fp32.hip and the register-resident kernels
+// the launchers choose between, as one unit.  TEST INFRASTRUCTURE ONLY -- see hip_emu.h.
 #include "emu_driver.h"
 #include "../../tiny-cuda-nn_amd/csrc/mlp_kernels.hip"
+#include "../../tiny-cuda-nn_amd/csrc/mlp_general_fp32.hip"
 #include "../../tiny-cuda-nn_amd/csrc/mlp_train_wave.hip"
 #include "../../tiny-cuda-nn_amd/csrc/mlp_train_wide.hip"
 #include "../../tiny-cuda-nn_amd/csrc/elementwise_kernels.h"  // reduce_sum (emu_driver_misc.cpp holds the kernels)
@@ -120,6 +122,42 @@ int emu_mlp_train_f32_input(const EmuMlp* e, uint32_t n, const uint16_t* params,
 		fin.enc_out = (half_t*)enc_out;
 		train(m, n, params, nullptr, &fin, MlpLossArgs{(LossType)loss_type, target, data_pdf, dims, loss_scale, n_total}, output, dL_doutput, dL_dinput_soa, grads, loss_sum);
 		return 0;
+	});
+}
+
+// ---- the fp32 network (mlp_general_fp32.hip; these entry points do not depend on -DTCNN_BF16) ----
+// input feature-major [in_width][n].  hidden: the saved stack (mlp_f32_saved_activation_bytes) or null (inference); output [n][padded_out],
+// or -- trimmed given (inference only) -- element (sample i, output j < dims) at trimmed[i * stride_i + j * stride_j].
+int emuf32_mlp_forward(const EmuMlp* e, uint32_t n, const float* params, const float* input_fm, float* hidden, float* output, float* trimmed, uint32_t dims,
+                       uint32_t stride_i, uint32_t stride_j) {
+	return emu_call(__func__, [&] {
+		MlpF32Output t;
+		if (trimmed) t = {trimmed, dims, stride_i, stride_j};
+		mlp_f32_forward(nullptr, make_mlp(e), n, params, input_fm, hidden, trimmed ? nullptr : output, t);
+	});
+}
+
+uint64_t emuf32_saved_activation_floats(const EmuMlp* e, uint32_t n) { return mlp_f32_saved_activation_bytes(make_mlp(e), n) / sizeof(float); }
+uint32_t emuf32_n_partials(const EmuMlp* e, uint32_t n) { return mlp_f32_n_partials(make_mlp(e), n); }
+
+// grads: float [n_params], overwritten unless `accumulate`; `output` is needed when the output activation is not None
+int emuf32_mlp_backward(const EmuMlp* e, uint32_t n, const float* params, const float* input_fm, const float* hidden, const float* dL_doutput, float* dL_dinput_fm, float* grads,
+                        int accumulate, const float* output) {
+	return emu_call(__func__, [&] {
+		const MlpMeta m = make_mlp(e);
+		std::vector<float> params_t(m.n_params(), -777.0f);
+		mlp_f32_transpose_weights(nullptr, m, params, params_t.data());
+		const uint32_t np = mlp_f32_n_partials(m, n);
+		std::vector<float> partials(grads ? (size_t)np * m.n_params() : 0, -12345.0f), dpre;
+		if (m.output_activation != (uint32_t)Activation::None) {
+			if (!output) throw std::runtime_error("output required");
+			dpre.resize((size_t)n * m.padded_out);
+			mlp_f32_output_activation_backward(nullptr, m, n, output, dL_doutput, dpre.data());
+			dL_doutput = dpre.data();
+		}
+		std::vector<float> workspace(mlp_f32_backward_workspace_bytes(m, n) / sizeof(float), -4321.0f);
+		mlp_f32_backward(nullptr, m, n, params_t.data(), input_fm, hidden, dL_doutput, dL_dinput_fm, grads ? partials.data() : nullptr, workspace.data());
+		if (grads) mlp_f32_finalize_gradients(nullptr, m, np, partials.data(), grads, accumulate != 0);
 	});
 }
 

@@ -1,48 +1,18 @@
-"""numpy front-end of the fp32 network kernels (csrc/mlp_general_f32.hip) on the host SIMT emulator.  TEST INFRASTRUCTURE ONLY.
+"""numpy front-end of the fp32 network kernels (csrc/mlp_general_fp32.hip) on the host SIMT emulator.  TEST INFRASTRUCTURE ONLY.
 
-The driver part is emu_driver_mlp_f32.cpp; it is built here into a library of its own, libtcnn_emu_mlp_f32.so, with emu.py's compile and
-link lines (imported, not copied): emu.py's part list is fixed, and folding this part into it is a later clean-up."""
+The entry points (emuf32_*) are in the network's driver part, emu_driver_mlp.cpp, of the one emulator library that emu.py builds and loads."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import emu
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_PART = os.path.join(_HERE, "emu_driver_mlp_f32.cpp")
-_LIB = os.path.join(_HERE, "libtcnn_emu_mlp_f32.so")
-_lib = None
-
-
-def build(force=False):
-    """Builds the library if it is missing or older than the driver, hip_emu.h / emu_driver.h or one of the csrc sources it includes."""
-    csrc = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "tiny-cuda-nn_amd", "csrc")
-    srcs = [_PART, os.path.join(_HERE, "hip_emu.h"), os.path.join(_HERE, "emu_driver.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    srcs.append(os.path.join(csrc, "mlp_general_f32.hip"))
-    if not force and os.path.exists(_LIB) and os.path.getmtime(_LIB) >= max(os.path.getmtime(s) for s in srcs):
-        return
-    with tempfile.TemporaryDirectory(dir=_HERE) as tmp:
-        obj = os.path.join(tmp, "emu_driver_mlp_f32.o")
-        subprocess.check_call(emu._COMPILE + [_PART, "-o", obj])
-        subprocess.check_call(emu._LINK + [obj, "-o", os.path.join(tmp, "lib.so")])
-        os.replace(os.path.join(tmp, "lib.so"), _LIB)
 
 
 def available():
     return emu.available()
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        build()
-        _lib = C.CDLL(_LIB)
-        _lib.emuf32_saved_activation_floats.restype = C.c_uint64
-        _lib.emuf32_n_partials.restype = C.c_uint32
-    return _lib
+lib = emu.lib
 
 
 def _p(a):

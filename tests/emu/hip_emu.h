@@ -306,6 +306,31 @@ inline f4 mfma_16x16x16(h4 a, h4 b, f4 c) {
 	return d;
 }
 
+// v_mfma_f32_16x16x4_f32: one float per lane and operand.  A[i][k]: lane = i + 16 k;  B[k][n]: lane = n + 16 k;  D as above.  A k-ordered
+// chain of fused multiply-adds, as on the device.
+inline f4 mfma_16x16x4_f32(float a, float b, f4 c) {
+	const unsigned lane = ::emu::g.cur->tidx.x & 63u;
+	::emu::Wave& w = ::emu::g.waves[::emu::g.cur->tidx.x / 64];
+	memcpy(&w.a[lane], &a, sizeof(float));
+	memcpy(&w.b[lane], &b, sizeof(float));
+	::emu::wave_barrier();
+	f4 d = c;
+	const unsigned col = lane & 15u, g = lane >> 4;
+	for (unsigned r = 0; r < 4; ++r) {
+		const unsigned row = 4 * g + r;
+		float s = c[r];
+		for (unsigned k = 0; k < 4; ++k) {
+			float av, bv;
+			memcpy(&av, &w.a[row + 16 * k], sizeof(float));
+			memcpy(&bv, &w.b[col + 16 * k], sizeof(float));
+			s = fmaf(av, bv, s);
+		}
+		d[r] = s;
+	}
+	::emu::wave_barrier();
+	return d;
+}
+
 // ds_read_b64_tr_b16: lane c of a 16-lane group, element j <- element (c & 3) of the word lane 4j + (c >> 2) addressed
 inline h4 lds_read_tr4(const half_t* word) {
 	const unsigned lane = ::emu::g.cur->tidx.x & 63u;

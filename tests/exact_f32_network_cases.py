@@ -1,4 +1,4 @@
-"""Exact-arithmetic cases for the fp32 network kernels (csrc/mlp_general_f32.hip), after the method of tests/exact_network_cases.py.
+"""Exact-arithmetic cases for the fp32 network kernels (csrc/mlp_general_fp32.hip), after the method of tests/exact_network_cases.py.
 
 Every weight, input and output gradient is a small dyadic rational, chosen so that EVERY product and EVERY partial sum of the passes -- a
 pre-activation, a backward product, a weight-gradient entry summed over the batch, any slab of it, the sum of the slabs -- is an fp32 number
@@ -8,7 +8,7 @@ output activation qualify.
 
 Helper, not a test:
   * CASES       the shapes: the smallest at which a tile, a K stage or a slab can go missing.  The layer kernel stages K in steps of
-                G32_BK = 32 floats and tiles m in blocks of 16 * {1..4}; the weight-gradient kernel works on 64 x 64 tiles and stages of 32
+                Gen<float>::BK = 32 floats and tiles m in blocks of 16 * {1..4}; the weight-gradient kernel works on 64 x 64 tiles and stages of 32
                 samples.  Hidden width 16: a single tile; 48: not a power of two, one and a half K stages; 272: eight full K stages plus a
                 ragged one (272 = 8 * 32 + 16), m tiles of 48 with a ragged last one, four full weight-gradient tiles and a ragged fifth.
                 Inputs 16 and 80 (two and a half K stages), outputs 3 (padded to 16) and 144 (> 128, three weight-gradient tiles), 1 and 3

@@ -1,4 +1,4 @@
-"""The fp32 network kernels (csrc/mlp_general_f32.hip) on the host SIMT emulator, no GPU: the exact cases of
+"""The fp32 network kernels (csrc/mlp_general_fp32.hip) on the host SIMT emulator, no GPU: the exact cases of
 tests/exact_f32_network_cases.py at n = 256 -- prediction, dL/dinput, weight gradients (Overwrite, and Accumulate into a non-zero dyadic
 buffer) and inference into a trimmed matrix in both layouts, all np.array_equal on bit patterns against the float64 evaluation cast to
 float32 -- and, first, the audit that makes that comparison legitimate, for every case including the n = 768 ones the GPU runs."""

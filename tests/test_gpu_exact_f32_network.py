@@ -1,4 +1,4 @@
-"""Bit-exact parity of the fp32 network (csrc/mlp_general_f32.hip) on a real MI355X, entry by entry, on inputs where the order of summation
+"""Bit-exact parity of the fp32 network (csrc/mlp_general_fp32.hip) on a real MI355X, entry by entry, on inputs where the order of summation
 cannot matter (tests/exact_f32_network_cases.py; the audit of every case runs on the CPU in tests/test_emu_f32_network.py).  Through the
 module entry points: prediction with its padded columns, inference, dL/dinput, the whole parameter gradient with GradientMode Overwrite and
 Accumulate (into a non-zero dyadic buffer), and inference into the caller's trimmed fp32 matrix in both layouts.  Every comparison is

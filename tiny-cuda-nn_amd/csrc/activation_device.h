@@ -3,7 +3,8 @@
 // (backward, expressed through the POST-activation value -- which is all that the fused kernels store).
 // SiLU and Sine (common_device.h:131-152 forward, :253-277 backward) have a derivative that needs the PRE-activation: only the
 // layer-by-layer network (mlp_general.hip) offers them, as hidden activations, through act_forward4_pre / act_backward4_pre below and a saved
-// stack with a second block (mlp_kernels.h mlp_saved_activation_bytes).  No other function of this file is entered with them.
+// stack with a second block (mlp_kernels.h mlp_saved_activation_bytes).  No other 16-bit function of this file is entered with them.
+// The fp32 network's activations (act32_*, all ten in one pair of bodies, nothing rounded) are at the end.
 #pragma once
 #include "tcnn_device.h"
 #if defined(TCNN_HOST_EMU)
@@ -239,6 +240,109 @@ TCNN_DEVICE float act_backward(uint32_t act, float v, half_t forward_value) {
 	if constexpr (GENERAL) {
 		if (act != (uint32_t)Activation::None) return act_backward_general(act, v, forward_value);
 	}
+	return v;
+}
+
+// ---- activations on fp32 values, for the fp32 layer-by-layer network (mlp_general_fp32.hip; common_device.h:108-186 forward, :363-418 and
+// :253-277 backward, with T = float): nothing is rounded.  ReLU / None stay inline as selects; everything else is ONE out-of-line body per
+// kernel, entered once per fragment, like the 16-bit functions above that they mirror.
+TCNN_DEVICE_NOINLINE f4 act32_forward4_general(uint32_t act, f4 x) {
+	f4 y;
+	switch ((Activation)act) {
+		case Activation::LeakyReLU:
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j) y[j] = x[j] > 0.0f ? x[j] : x[j] * 0.01f;
+			break;
+		case Activation::Exponential:
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j) y[j] = expf(x[j]);
+			break;
+		case Activation::Sigmoid:
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j) y[j] = 1.0f / (1.0f + expf(-x[j]));
+			break;
+		case Activation::Squareplus:
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j) {
+				const float t = x[j] * K_ACT;
+				y[j] = 0.5f * (t + sqrtf(t * t + 4.0f)) / K_ACT;
+			}
+			break;
+		case Activation::Softplus:
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j) y[j] = logf(expf(x[j] * K_ACT) + 1.0f) / K_ACT;
+			break;
+		case Activation::Tanh:
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j) y[j] = tanhf(x[j]);
+			break;
+		case Activation::SiLU:
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j) y[j] = x[j] * (1.0f / (1.0f + expf(-x[j])));
+			break;
+		case Activation::Sine:  // the accurate sinf: first-layer pre-activations of a SIREN network are tens of radians
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j) y[j] = sinf(x[j]);
+			break;
+		case Activation::ReLU:
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j) y[j] = x[j] > 0.0f ? x[j] : 0.0f;
+			break;
+		default: y = x; break;
+	}
+	return y;
+}
+template <bool GENERAL>
+TCNN_DEVICE f4 act32_forward4(uint32_t act, f4 x) {
+	if constexpr (GENERAL) {
+		mfma_settle(x);  // the fragment is read on both sides of the branch below
+		if (act != (uint32_t)Activation::None && act != (uint32_t)Activation::ReLU) x = act32_forward4_general(act, x);
+	}
+	const bool relu = act == (uint32_t)Activation::ReLU;  // a select on a uniform flag, not a branch behind the MFMA (act_forward4)
+#pragma unroll
+	for (uint32_t j = 0; j < 4; ++j) x[j] = (relu && !(x[j] > 0.0f)) ? 0.0f : x[j];
+	return x;
+}
+// v * f'(.) with f' through `aux`: the post-activation value, or -- SiLU / Sine -- the pre-activation
+TCNN_DEVICE_NOINLINE f4 act32_backward4_general(uint32_t act, f4 v, f4 aux) {
+	f4 out;
+#pragma unroll
+	for (uint32_t j = 0; j < 4; ++j) {
+		const float y = aux[j];
+		float factor = 1.0f;
+		switch ((Activation)act) {  // (uniform: hoisted out of the unrolled loop)
+			case Activation::ReLU: factor = y > 0.0f ? 1.0f : 0.0f; break;
+			case Activation::LeakyReLU: factor = y > 0.0f ? 1.0f : 0.01f; break;
+			case Activation::Exponential: factor = y; break;
+			case Activation::Sigmoid: factor = y * (1.0f - y); break;
+			case Activation::Squareplus: {
+				const float t = y * K_ACT;
+				factor = t * t / (t * t + 1.0f);
+				break;
+			}
+			case Activation::Softplus: factor = 1.0f - expf(-y * K_ACT); break;
+			case Activation::Tanh: factor = 1.0f - y * y; break;
+			case Activation::SiLU: {
+				const float l = 1.0f / (1.0f + expf(-y));
+				factor = l + y * (l * (1.0f - l));
+				break;
+			}
+			case Activation::Sine: factor = cosf(y); break;
+			default: break;
+		}
+		out[j] = v[j] * factor;
+	}
+	return out;
+}
+template <bool GENERAL>
+TCNN_DEVICE f4 act32_backward4(uint32_t act, f4 v, f4 aux) {
+	if constexpr (GENERAL) {
+		mfma_settle(v);
+		if (act != (uint32_t)Activation::None && act != (uint32_t)Activation::ReLU) v = act32_backward4_general(act, v, aux);
+	}
+	const bool relu = act == (uint32_t)Activation::ReLU;
+#pragma unroll
+	for (uint32_t j = 0; j < 4; ++j) v[j] = (relu && !(aux[j] > 0.0f)) ? 0.0f : v[j];
 	return v;
 }
 

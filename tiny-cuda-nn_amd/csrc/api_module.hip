@@ -22,7 +22,7 @@ struct tcnn_module {
 	// FP32_GRADIENT_TARGET (found on the device per call) and the results scaled back, exactly.
 	bool fp32_io = false;
 	// tcnn_create_network[_with_input_encoding]_precision(..., TCNN_PRECISION_FP32): the network is the fp32 layer-by-layer one
-	// (NetworkDesc::fp32, mlp_general_f32.h) behind the encoding's fp32 path; fp32_io is set as well (precisions, no 16-bit inputs)
+	// (NetworkDesc::fp32, mlp_kernels.h mlp_f32_*) behind the encoding's fp32 path; fp32_io is set as well (precisions, no 16-bit inputs)
 	bool fp32_network() const { return fp32_io && md.has_network; }
 };
 static constexpr float FP32_GRADIENT_SCALE = 1024.0f, FP32_GRADIENT_TARGET = 16384.0f;

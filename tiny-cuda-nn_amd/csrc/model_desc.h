@@ -63,7 +63,7 @@ struct NetworkDesc {
 	uint32_t n_output_dims = 0;
 	uint32_t n_hidden_layers = 0;
 	std::string otype;
-	// weights, activations and gradients are float and the network is the fp32 layer-by-layer one (mlp_general_f32.h) under every `otype`
+	// weights, activations and gradients are float and the network is the fp32 layer-by-layer one (mlp_kernels.h mlp_f32_*) under every `otype`
 	// spelling: what the reference built without half precision makes of every network (network.cu:51-138 with network_precision_t = float)
 	bool fp32 = false;
 	Json hyperparams() const;  // fully_fused_mlp.h:139-147

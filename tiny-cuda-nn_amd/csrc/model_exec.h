@@ -115,7 +115,7 @@ void model_forward(hipStream_t stream, Profiler* profiler, const Model& md, cons
 void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const half_t* dL_doutput,
                     half_t* dL_dparams, const float* input, const half_t* output, const half_t* params, int gradient_mode,
                     uint32_t lds_level_budget, half_t* dL_dinput16 = nullptr);  // dL_dinput16: of a context made with input16, instead of dL_dinput
-// The same two passes of a model whose network is the fp32 one (NetworkDesc::fp32, mlp_general_f32.h): parameters, output, dL_doutput and
+// The same two passes of a model whose network is the fp32 one (NetworkDesc::fp32, mlp_kernels.h mlp_f32_*): parameters, output, dL_doutput and
 // dL_dparams are float, the encoding runs its fp32 path (encoding_forward<float> / encoding_backward<float>) and hands the network an fp32
 // feature-major matrix; the context keeps that matrix and the saved fp32 activations.  trimmed (inference only, ctx == nullptr): the result
 // goes to the caller's trimmed matrix instead of `output`.

@@ -5,7 +5,6 @@
 
 #include "half_input_kernels.h"
 #include "host_common.h"
-#include "mlp_general_f32.h"
 #include "switches.h"
 
 namespace tcnn_hip {
@@ -359,7 +358,7 @@ void model_backward(hipStream_t stream, Profiler* profiler, const Model& md, con
 	encoding_share(dL_denc, stride_k, stride_i);
 }
 
-// ---- the fp32 network (mlp_general_f32.h) behind the encoding's fp32 path --------------------------------------------------------------
+// ---- the fp32 network (mlp_kernels.h mlp_f32_*) behind the encoding's fp32 path --------------------------------------------------------------
 void model_forward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, float* output, const float* params, ForwardCtx* ctx,
                        bool prepare_input_gradients, const MlpF32Output* trimmed) {
 	if (!md.has_network || !md.net.fp32) throw std::runtime_error("model_forward_f32: not an fp32 network");

@@ -100,9 +100,11 @@ constexpr float LOSS_SCALE_FP16 = 128.0f;          // reference common.h:243
 // MFMA wrappers.  Fragment maps (cdna_hip_programming.md section 3):
 //   16x16x32 f16:  A[i = lane&15][k = 8*(lane>>4) + j], B[k = 8*(lane>>4) + j][n = lane&15], j<8
 //   16x16x16 f16:  A[i = lane&15][k = 4*(lane>>4) + j], B[k = 4*(lane>>4) + j][n = lane&15], j<4
-//   C/D (both):    row = 4*(lane>>4) + r, col = lane&15, r<4
+//   16x16x4 f32:   A[i = lane&15][k = lane>>4], B[k = lane>>4][n = lane&15]: ONE float per lane and operand, a k-ordered fmaf chain
+//   C/D (all):     row = 4*(lane>>4) + r, col = lane&15, r<4
 // ---------------------------------------------------------------------------------------------
 #if !defined(TCNN_HOST_EMU)
+TCNN_DEVICE f4 mfma_16x16x4_f32(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 #if defined(TCNN_BF16)
 typedef short bf16_bits2 __attribute__((ext_vector_type(2)));
 typedef short bf16_bits4 __attribute__((ext_vector_type(4)));
