@@ -92,8 +92,9 @@ int tcnn_create_encoding(uint32_t n_input_dims, const char* encoding_json, int r
  * the 16-bit network's element for element, and tcnn_module_initialize_params writes the fp32 values the 16-bit network rounds its own from.
  * The input encoding runs its fp32 path (every encoding of this build, Composite included) and hands the network an fp32 matrix.
  * param_precision() / output_precision() report TCNN_PRECISION_FP32 (tcnn_default_loss_scale: 1), every `void*` of inference / forward /
- * backward carries float, tcnn_module_supports_half_input answers 0, backward_backward_input stays "not implemented" as for every network,
- * and the max_level entries work where the encoding is a lone grid.
+ * backward carries float, tcnn_module_supports_half_input answers 0, and the max_level entries work where the encoding is a lone grid.
+ * backward_backward_input (below) is implemented for the modules tcnn_create_network_precision makes -- the Identity encoding with scale 1
+ * and offset 0 in front -- and stays "not implemented" behind every other encoding, as for the 16-bit networks.
  * Out of scope, TCNN_ERROR_UNSUPPORTED: an fp32 TRAINER -- tcnn_create_from_config_precision(..., TCNN_PRECISION_FP32) refuses by name (the
  * fused loss and optimizer launches are 16-bit), and with it training_step and the data-parallel entry points, which take trainable models
  * only.  With the library's own precision it is tcnn_create_from_config. */
@@ -112,10 +113,16 @@ int tcnn_module_backward(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_cont
                          float* dL_dinput, const void* dL_doutput, void* dL_dparams, const float* input,
                          const void* output, const void* params);
 /* cpp_api.h:106-108 -> DifferentiableObject::backward_backward_input: second-order pass through dL_dinput.  Like the
- * reference, implemented by the grid encoding only (grid.h:910-1042); TCNN_ERROR_UNSUPPORTED for every other module.
- * dL_ddLdinput: fp32 [n][n_input_dims] (required); the three outputs dL_dparams (fp16, overwritten), dL_ddLdoutput (fp16
- * [n][padded width]) and dL_dinput (fp32, overwritten) are each optional; the context must come from a forward pass with
- * prepare_input_gradients. */
+ * reference, implemented by the grid encoding (grid.h:910-1042) -- and, beyond the reference, by the fp32 networks of
+ * tcnn_create_network_precision(..., TCNN_PRECISION_FP32): the double backward through the MLP, every width, depth, hidden and output
+ * activation of that network (what an eikonal or curvature loss on the network's input gradient needs).  TCNN_ERROR_UNSUPPORTED for every
+ * other module: 16-bit networks, an fp32 network behind any other encoding, Composite and parameterless encodings.
+ * dL_ddLdinput: fp32 [n][n_input_dims] (required); the three outputs dL_dparams (the module's parameter precision, overwritten),
+ * dL_ddLdoutput (its output precision, [n][padded width]) and dL_dinput (fp32, overwritten) are each optional, and only the passes a
+ * requested one needs are launched; dL_doutput is required for dL_dparams and dL_dinput, and a network also needs `params`.  A grid's
+ * context must come from a forward pass with prepare_input_gradients.  The network's dL_doutput is the gradient with respect to its
+ * OUTPUT (an output activation's derivatives are taken inside); its dL_dinput is zero where neither activation has a second derivative
+ * (None, ReLU, LeakyReLU). */
 int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream, const tcnn_context_t* ctx, uint32_t n_elements,
                                         const float* dL_ddLdinput, const float* input, const void* dL_doutput,
                                         void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput, const void* params);

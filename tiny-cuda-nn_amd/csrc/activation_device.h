@@ -346,4 +346,44 @@ TCNN_DEVICE f4 act32_backward4(uint32_t act, f4 v, f4 aux) {
 	return v;
 }
 
+// ---- second derivatives, for the fp32 network's second-order pass (mlp_general_impl.h gen_backward_backward).  Through the same `aux` as
+// the first: the post-activation value, or -- SiLU / Sine -- the pre-activation.  None, ReLU and LeakyReLU are piecewise linear: their second
+// derivative is zero everywhere the first exists, and the pass skips every term that carries it.
+TCNN_HOST_DEVICE bool act_second_derivative_is_zero(uint32_t act) {
+	return act == (uint32_t)Activation::None || act == (uint32_t)Activation::ReLU || act == (uint32_t)Activation::LeakyReLU;
+}
+// v * f''(.)
+TCNN_DEVICE_NOINLINE f4 act32_second4_general(uint32_t act, f4 v, f4 aux) {
+	f4 out;
+#pragma unroll
+	for (uint32_t j = 0; j < 4; ++j) {
+		const float y = aux[j];
+		float factor = 0.0f;
+		switch ((Activation)act) {  // (uniform: hoisted out of the unrolled loop)
+			case Activation::Exponential: factor = y; break;
+			case Activation::Sigmoid: factor = y * (1.0f - y) * (1.0f - 2.0f * y); break;
+			case Activation::Squareplus: {
+				const float t = y * K_ACT, q = t * t + 1.0f;
+				factor = (t * t / q) * (2.0f * t * K_ACT / (q * q));
+				break;
+			}
+			case Activation::Softplus: {
+				const float s = 1.0f - expf(-y * K_ACT);
+				factor = K_ACT * s * (1.0f - s);
+				break;
+			}
+			case Activation::Tanh: factor = -2.0f * y * (1.0f - y * y); break;
+			case Activation::SiLU: {
+				const float l = 1.0f / (1.0f + expf(-y));
+				factor = l * (1.0f - l) * (2.0f + y * (1.0f - 2.0f * l));
+				break;
+			}
+			case Activation::Sine: factor = -sinf(y); break;
+			default: break;
+		}
+		out[j] = v[j] * factor;
+	}
+	return out;
+}
+
 }  // namespace tcnn_hip

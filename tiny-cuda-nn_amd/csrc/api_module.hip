@@ -246,10 +246,24 @@ int tcnn_module_backward_half_input(tcnn_module_t* m, tcnn_stream_t stream, cons
 }
 
 // cpp_api.cu:117-135 -> DifferentiableObject::backward_backward_input, implemented by the grid encoding only in the
-// reference (grid.h:910-1042; object.h:468 throws for everything else).
+// reference (grid.h:910-1042; object.h:468 throws for everything else).  Beyond the reference: the fp32 networks of
+// tcnn_create_network_precision (model_exec.h model_backward_backward_f32), the double backward through the MLP that eikonal and
+// curvature losses on a network need.
 int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_, const tcnn_context_t* ctx, uint32_t n, const float* dL_ddLdinput,
                                         const float* input, const void* dL_doutput, void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput,
                                         const void* params) {
+	if (m->fp32_network() && fp32_second_order_network(m->md)) {
+		TCNN_API_BEGIN
+		if (!ctx) throw std::runtime_error("backward_backward_input: missing forward context");
+		model_backward_backward_f32((hipStream_t)stream_, m->md, IoLayout::dense(m->md), ctx->ctx, n, dL_ddLdinput, (const float*)dL_doutput, (float*)dL_dparams, (float*)dL_ddLdoutput,
+		                            dL_dinput, (const float*)params);
+		TCNN_API_END
+	}
+	if (m->fp32_network() && m->md.enc.is_grid()) {  // same refusal, and what gives the same result today
+		set_last_error("DifferentiableObject::backward_backward_input_impl: not implemented error: the second-order pass of an fp32 network takes the plain Identity encoding "
+		               "(tcnn_create_network_precision); Encoding and Network composed in torch give the same result");
+		return TCNN_ERROR_UNSUPPORTED;
+	}
 	if (m->md.has_network || !m->md.enc.is_grid()) {
 		set_last_error("DifferentiableObject::backward_backward_input_impl: not implemented error");  // object.h:478
 		return TCNN_ERROR_UNSUPPORTED;

@@ -49,6 +49,7 @@
 #include <algorithm>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace tcnn_hip {
@@ -74,7 +75,12 @@ struct Gen;
 
 // _PRE (16-bit only): the epilogues of the activations that keep their pre-activation (SiLU / Sine, activation_device.h act_forward4_pre /
 // act_backward4_pre).  _TRIMMED: GEN_EPI_FORWARD whose result goes to the caller's fp32 matrix (Yt ...) instead of Y
-enum : uint32_t { GEN_EPI_NONE = 0, GEN_EPI_FORWARD = 1, GEN_EPI_BACKWARD = 2, GEN_EPI_FORWARD_PRE = 3, GEN_EPI_BACKWARD_PRE = 4, GEN_EPI_FORWARD_TRIMMED = 5 };
+// _DERIVATIVE_RAW / _CURVATURE (fp32 only): the epilogues of the second-order pass (gen_backward_backward below).  _DERIVATIVE_RAW is
+// GEN_EPI_BACKWARD that also keeps the raw accumulator (through P); _CURVATURE adds the term with the activation's second derivative.
+enum : uint32_t {
+	GEN_EPI_NONE = 0, GEN_EPI_FORWARD = 1, GEN_EPI_BACKWARD = 2, GEN_EPI_FORWARD_PRE = 3, GEN_EPI_BACKWARD_PRE = 4, GEN_EPI_FORWARD_TRIMMED = 5,
+	GEN_EPI_DERIVATIVE_RAW = 6, GEN_EPI_CURVATURE = 7
+};
 
 template <typename T>
 struct GenLayerArgs {
@@ -84,14 +90,19 @@ struct GenLayerArgs {
 	uint32_t ldx;
 	T* Y;                 // sample-major [n][ldy], or feature-major [M][n] (Y_FM)
 	uint32_t ldy;
-	const T* F;           // GEN_EPI_BACKWARD: the values the derivative is taken at, sample-major [n][ldf]: post-activations (fp32 SiLU / Sine:
-	uint32_t ldf;         // pre-activations).  GEN_EPI_BACKWARD_PRE: the PRE-activation values, same layout
+	const T* F;           // GEN_EPI_BACKWARD, _DERIVATIVE_RAW, _CURVATURE: the values the derivative is taken at, sample-major [n][ldf]:
+	uint32_t ldf;         // post-activations (fp32 SiLU / Sine: pre-activations).  GEN_EPI_BACKWARD_PRE: the PRE-activation values, same layout
 	uint32_t act;
-	T* P;                 // GEN_EPI_FORWARD_PRE, fp32 GEN_EPI_FORWARD: where the pre-activations go, sample-major [n][ldy]; null: not saved
+	T* P;                 // GEN_EPI_FORWARD_PRE, fp32 GEN_EPI_FORWARD: where the pre-activations go, sample-major [n][ldy]; null: not saved.
+	                      // GEN_EPI_DERIVATIVE_RAW: where the raw accumulator goes, same layout; null: not kept
 	// GEN_EPI_FORWARD_TRIMMED: element (sample i, m) with m < t_dims at Yt[i * t_stride_i + m * t_stride_j].  t_vec: floats per store the host
 	// proved aligned for EVERY (sample, m = multiple of 4) -- 4 or 2 only with t_stride_j == 1 (gen_trimmed_vec) -- else 1
 	float* Yt;
 	uint32_t t_dims, t_stride_i, t_stride_j, t_vec;
+	// GEN_EPI_CURVATURE: Y = acc * act'(F) + E * Tn * act''(F), the two factors sample-major [n][ldy] like Y.  Y may BE E (each fragment is
+	// read and written by the one lane that holds it, the reads first)
+	const T* E;
+	const T* Tn;
 };
 
 // the 4 values of one accumulator fragment (m .. m + 3 of one sample) into the caller's fp32 matrix: one 16-byte store where the host
@@ -124,6 +135,7 @@ __global__ void __launch_bounds__(GEN_THREADS) k_mlp_general_layer(const GenLaye
 	typedef typename G::vec vec;
 	typedef typename G::frag frag;
 	static_assert(G::PRE_EPILOGUES || (EPI != GEN_EPI_FORWARD_PRE && EPI != GEN_EPI_BACKWARD_PRE), "the fp32 network has no _PRE instances");
+	static_assert(!G::PRE_EPILOGUES || (EPI != GEN_EPI_DERIVATIVE_RAW && EPI != GEN_EPI_CURVATURE), "the second-order pass is the fp32 network's");
 	constexpr uint32_t VE = G::VE, BK = G::BK, LDK = G::LDK, KR = 4 * VE;  // KR: k per operand read of a wave (4 lane groups x one chunk)
 	constexpr uint32_t BM = 16 * NMB, CK = BK / VE;                        // CK: 16-byte chunks per row of a stage
 	constexpr uint32_t W_CHUNKS = BM * CK, X_CHUNKS = GEN_BN * CK;
@@ -245,6 +257,17 @@ __global__ void __launch_bounds__(GEN_THREADS) k_mlp_general_layer(const GenLaye
 			} else if constexpr (EPI == GEN_EPI_BACKWARD) {
 				const frag fv = *(const frag*)(a.F + sample * a.ldf + m);
 				o = G::template backward<GENERAL>(a.act, acc[mb][sb], fv);
+			} else if constexpr (EPI == GEN_EPI_DERIVATIVE_RAW) {
+				// the tangent pass (forward weights: t and u = t * act') and the first-order recomputation (transposed weights: e and d = e * act')
+				const frag fv = *(const frag*)(a.F + sample * a.ldf + m);
+				o = G::template backward<GENERAL>(a.act, acc[mb][sb], fv);
+				if (valid && a.P) *(frag*)(a.P + sample * a.ldy + m) = G::narrow(acc[mb][sb]);
+			} else if constexpr (EPI == GEN_EPI_CURVATURE) {
+				// all three fragments in flight before anything is computed or stored; no element-wise pass over [n][W] beside the product
+				const frag fv = *(const frag*)(a.F + sample * a.ldf + m);
+				const frag ev = *(const frag*)(a.E + sample * a.ldy + m);
+				const frag tv = *(const frag*)(a.Tn + sample * a.ldy + m);
+				o = G::curvature(a.act, acc[mb][sb], ev, tv, fv);
 			} else if constexpr (EPI == GEN_EPI_FORWARD_PRE) {
 				// one launch where the reference runs a product and an element-wise pass: the rounded accumulator is the saved
 				// pre-activation AND the activation's argument.  Both stores behind everything this iteration computes; it loads nothing.
@@ -283,9 +306,19 @@ struct GenWgradArgs {
 	size_t slab_stride, matrix_offset;
 	uint32_t n_slices;
 };
+// with a second operand pair in the layouts of the first: the tile is sum_s d[s][o] a[s][i] + sum_s d2[s][o] a2[s][i].  An argument block of
+// its own, so that the single-pair instances keep theirs (and their code) as they were
+template <typename T>
+struct GenWgradDualArgs : GenWgradArgs<T> {
+	const T* d2;
+	const T* a2;
+};
 
-template <typename T, bool A_FM>
-__global__ void __launch_bounds__(GEN_THREADS) k_mlp_general_wgrad(const GenWgradArgs<T> p) {
+// ARGS = GenWgradDualArgs (the second-order pass, mlp_f32_backward_backward): every slice runs its stages of the first pair, then the same
+// stages of the second, into the same accumulators -- one launch and one slab entry per matrix element, the order of the terms fixed.
+template <typename T, bool A_FM, typename ARGS = GenWgradArgs<T>>
+__global__ void __launch_bounds__(GEN_THREADS) k_mlp_general_wgrad(const ARGS p) {
+	constexpr bool DUAL = !std::is_same<ARGS, GenWgradArgs<T>>::value;
 	typedef Gen<T> G;
 	typedef typename G::vec vec;
 	constexpr uint32_t TILE = GEN_WG_TILE, VE = G::VE, BS = G::WG_BS, LDT = G::WG_LDT, LDF = G::WG_LDF, CK = TILE / VE, CS = BS / VE;
@@ -300,11 +333,21 @@ __global__ void __launch_bounds__(GEN_THREADS) k_mlp_general_wgrad(const GenWgra
 	const uint32_t tile = blockIdx.x % n_tiles, slice = blockIdx.x / n_tiles;
 	const uint32_t o0 = (tile / n_ti) * TILE, i0 = (tile % n_ti) * TILE;
 	const uint32_t n_stages = p.n / BS;
-	const uint32_t t_begin = (uint32_t)((uint64_t)slice * n_stages / p.n_slices), t_end = (uint32_t)((uint64_t)(slice + 1) * n_stages / p.n_slices);
+	const uint32_t t_begin = (uint32_t)((uint64_t)slice * n_stages / p.n_slices), t_second = (uint32_t)((uint64_t)(slice + 1) * n_stages / p.n_slices);
+	const uint32_t t_end = DUAL ? 2u * t_second - t_begin : t_second;  // DUAL: stage t >= t_second is stage t - (t_second - t_begin) of the second pair
 	const vec zero = G::zero();
 
 	vec dreg[PER], areg[PER];
 	auto load = [&](uint32_t t) {
+		const T* pd = p.d;
+		const T* pa = p.a;
+		if constexpr (DUAL) {
+			if (t >= t_second) {  // (uniform)
+				t -= t_second - t_begin;
+				pd = p.d2;
+				pa = p.a2;
+			}
+		}
 		const size_t s = (size_t)t * BS;
 #pragma unroll
 		for (uint32_t q = 0; q < PER; ++q) {
@@ -312,18 +355,18 @@ __global__ void __launch_bounds__(GEN_THREADS) k_mlp_general_wgrad(const GenWgra
 			{
 				const uint32_t row = c / CK, cc = c % CK;
 				const bool valid = o0 + VE * cc < p.WO;
-				const vec v = *(const vec*)(p.d + (s + row) * p.ldd + (valid ? o0 + VE * cc : 0u));
+				const vec v = *(const vec*)(pd + (s + row) * p.ldd + (valid ? o0 + VE * cc : 0u));
 				dreg[q] = valid ? v : zero;
 			}
 			if constexpr (A_FM) {  // row = feature, cc = chunk of samples
 				const uint32_t row = c / CS, cc = c % CS;
 				const bool valid = i0 + row < p.WI;
-				const vec v = *(const vec*)(p.a + (size_t)(valid ? i0 + row : 0u) * p.n + s + VE * cc);
+				const vec v = *(const vec*)(pa + (size_t)(valid ? i0 + row : 0u) * p.n + s + VE * cc);
 				areg[q] = valid ? v : zero;
 			} else {
 				const uint32_t row = c / CK, cc = c % CK;
 				const bool valid = i0 + VE * cc < p.WI;
-				const vec v = *(const vec*)(p.a + (s + row) * p.lda + (valid ? i0 + VE * cc : 0u));
+				const vec v = *(const vec*)(pa + (s + row) * p.lda + (valid ? i0 + VE * cc : 0u));
 				areg[q] = valid ? v : zero;
 			}
 		}
@@ -416,9 +459,10 @@ static void gen_launch_layer(hipStream_t stream, const GenLayerArgs<T>& a) {
 	const dim3 grid(div_round_up(a.M, 16u * nmb) * (a.n / GEN_BN)), block(GEN_THREADS);
 	const uint32_t lds_bytes = 2u * (16u * nmb + GEN_BN) * Gen<T>::LDK * (uint32_t)sizeof(T);  // <= 54 KiB
 	const bool general = EPI != GEN_EPI_NONE && !act_is_simple(a.act);
-	// the _PRE epilogues have one instance per tile shape (GENERAL says nothing there); the other instances are what they were
+	// the _PRE and _CURVATURE epilogues have one instance per tile shape (GENERAL says nothing there: _CURVATURE is launched for the
+	// activations with a second derivative only); the other instances are what they were
 #define TCNN_GEN_LAUNCH(NMB_)                                                                                                   \
-	if constexpr (EPI == GEN_EPI_FORWARD_PRE || EPI == GEN_EPI_BACKWARD_PRE) {                                                  \
+	if constexpr (EPI == GEN_EPI_FORWARD_PRE || EPI == GEN_EPI_BACKWARD_PRE || EPI == GEN_EPI_CURVATURE) {                      \
 		TCNN_LAUNCH((k_mlp_general_layer<T, NMB_, EPI, X_FM, Y_FM, true>), grid, block, lds_bytes, stream, a);                  \
 	} else if (general) {                                                                                                       \
 		TCNN_LAUNCH((k_mlp_general_layer<T, NMB_, EPI, X_FM, Y_FM, EPI != GEN_EPI_NONE>), grid, block, lds_bytes, stream, a);   \

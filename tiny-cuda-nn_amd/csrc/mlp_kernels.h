@@ -240,5 +240,15 @@ void mlp_f32_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const fl
                       float* dL_dinput, float* partials, void* workspace);
 // grads[i] = (accumulate ? grads[i] : 0) + (partials[0][i] + partials[1][i] + ...), slabs in ascending order
 void mlp_f32_finalize_gradients(hipStream_t stream, const MlpMeta& m, uint32_t n_partials, const float* partials, float* grads, bool accumulate);
+// The second-order pass: the gradients of S = <v, dL/dinput> (dL/dinput as mlp_f32_backward computes it from the caller's dL_doutput, taken
+// w.r.t. the network's OUTPUT here: the output activation's derivative is applied inside) with respect to dL_doutput, the network input and the
+// weights.  v: feature-major [in_width][n] like `input`, zero in the rows the encoding padded.  Each of the three results may be null, and
+// only the launches a requested one needs are made: dL_ddLdoutput [n][padded_out]; dL_dinput feature-major [in_width][n]; partials
+// ([mlp_f32_n_partials][n_params], to be summed by mlp_f32_finalize_gradients).  dL_doutput and params_t are needed for the last two only.
+// Where neither activation has a second derivative (None / ReLU / LeakyReLU) dL_dinput is zeros.
+bool mlp_f32_second_order_has_curvature(const MlpMeta& m);
+size_t mlp_f32_backward_backward_workspace_bytes(const MlpMeta& m, uint32_t n);
+void mlp_f32_backward_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* params, const float* params_t, const float* input, const float* hidden,
+                               const float* v, const float* dL_doutput, float* dL_ddLdoutput, float* dL_dinput, float* partials, void* workspace);
 
 }  // namespace tcnn_hip

@@ -123,6 +123,13 @@ void model_forward_f32(hipStream_t stream, const Model& md, const IoLayout& layo
                        bool prepare_input_gradients, const MlpF32Output* trimmed = nullptr);
 void model_backward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const float* dL_doutput, float* dL_dparams,
                         const float* input, const float* output, const float* params, int gradient_mode);
+// The second-order pass (backward_backward_input) of the modules tcnn_create_network_precision(..., TCNN_PRECISION_FP32) makes -- an fp32
+// network behind the Identity encoding with scale 1 and offset 0, which fp32_second_order_network tells: the gradients of
+// <dL_ddLdinput, dL_dinput> with respect to dL_doutput ([n][padded outputs]), the parameters (overwritten) and the input ([n][n_input_dims]).
+// Each result may be null; dL_doutput is needed for the last two.  `ctx` is the forward pass's (encoded input, saved activations).
+bool fp32_second_order_network(const Model& md);
+void model_backward_backward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, const float* dL_ddLdinput, const float* dL_doutput,
+                                 float* dL_dparams, float* dL_ddLdoutput, float* dL_dinput, const float* params);
 // network->inference into the caller's fp32 matrix (object.h:214-271)
 void inference_to_f32(hipStream_t stream, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const half_t* params, float* out, uint32_t stride_i, uint32_t stride_j);
 

@@ -407,6 +407,47 @@ void model_backward_f32(hipStream_t stream, const Model& md, const IoLayout& lay
 	if (need_denc) encoding_backward(stream, nullptr, md, layout, ctx, n, dL_dinput, (const float*)denc.as<float>(), n, 1u, dL_dparams, want_grads, accumulate, input);
 }
 
+bool fp32_second_order_network(const Model& md) {
+	const EncodingDesc& e = md.enc;
+	return md.has_network && md.net.fp32 && e.kind == EncodingKind::Identity && e.id_scale == 1.0f && e.id_offset == 0.0f;
+}
+
+// The second-order pass of an fp32 network behind the plain Identity encoding (fp32_second_order_network): mlp_f32_backward_backward between
+// the encoding's two linear steps -- v = dL_ddLdinput padded with zeros into the network's feature-major input layout, and the network's
+// dL/d(encoded input) trimmed back to the caller's [n][n_input_dims].  dL_dparams is overwritten, as by tcnn_module_backward.
+void model_backward_backward_f32(hipStream_t stream, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, const float* dL_ddLdinput, const float* dL_doutput,
+                                 float* dL_dparams, float* dL_ddLdoutput, float* dL_dinput, const float* params) {
+	if (!fp32_second_order_network(md)) throw std::runtime_error("model_backward_backward_f32: not an fp32 network behind the plain Identity encoding");
+	check_batch(n, widest_matrix(md));
+	if (n == 0) return;
+	if (ctx.n != n) throw std::runtime_error("backward_backward_input: batch size does not match the forward context");
+	if (!dL_ddLdinput) throw std::runtime_error("backward_backward_input: dL_ddLdinput is required");
+	if (!ctx.enc.ptr || !ctx.hidden.ptr) throw std::runtime_error("backward_backward_input: this context holds no saved activations of an fp32 network");
+	if (!dL_dparams && !dL_ddLdoutput && !dL_dinput) return;
+	if ((dL_dparams || dL_dinput) && !dL_doutput) throw std::runtime_error("backward_backward_input: dL_doutput is required for parameter / input gradients");
+	if (!params) throw std::runtime_error("backward_backward_input: params are required");
+	const EncodingDesc& e = md.enc;
+	const MlpMeta& mlp = md.net.mlp;
+	const uint32_t IN = e.padded_output_width;
+	const bool transposed = dL_dparams || (dL_dinput && mlp_f32_second_order_has_curvature(mlp));
+	Scratch v(stream, (size_t)IN * n * sizeof(float));
+	identity_forward(stream, n, e.n_dims, e.n_dims, 1.0f, 0.0f, dL_ddLdinput, md.n_input_dims, 1u, v.as<float>(), n, 1u);
+	if (IN > e.n_dims) HIP_CHECK(hipMemsetAsync(v.as<float>() + (size_t)e.n_dims * n, 0, (size_t)(IN - e.n_dims) * n * sizeof(float), stream));
+	Scratch params_t, partials, denc;
+	if (transposed) {
+		params_t = Scratch(stream, md.n_mlp_params() * sizeof(float));
+		mlp_f32_transpose_weights(stream, mlp, params, params_t.as<float>());
+	}
+	const uint32_t n_partials = mlp_f32_n_partials(mlp, n);
+	if (dL_dparams) partials = Scratch(stream, (size_t)n_partials * md.n_mlp_params() * sizeof(float));
+	if (dL_dinput) denc = Scratch(stream, (size_t)IN * n * sizeof(float));
+	Scratch workspace(stream, mlp_f32_backward_backward_workspace_bytes(mlp, n));
+	mlp_f32_backward_backward(stream, mlp, n, params, transposed ? params_t.as<float>() : nullptr, ctx.enc.as<float>(), ctx.hidden.as<float>(), v.as<float>(), dL_doutput, dL_ddLdoutput,
+	                          dL_dinput ? denc.as<float>() : nullptr, dL_dparams ? partials.as<float>() : nullptr, workspace.ptr);
+	if (dL_dparams) mlp_f32_finalize_gradients(stream, mlp, n_partials, partials.as<float>(), dL_dparams, false);
+	if (dL_dinput) identity_backward(stream, n, e.n_dims, 1.0f, (const float*)denc.as<float>(), n, 1u, dL_dinput, layout.dx_stride_i, layout.dx_stride_d);
+}
+
 static void grid_backward_phase_hook(void* user, int phase, int begin) {
 	PhaseTimer& t = *(PhaseTimer*)user;
 	Profiler* p = t.profiler;

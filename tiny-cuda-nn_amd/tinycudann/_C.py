@@ -509,8 +509,9 @@ class Module:
             return dL_dinput, dL_dparams
 
     def bwd_bwd_input(self, ctx, input, params, dL_ddLdinput, dL_doutput):  # bindings.cpp:193-241
-        """Second-order pass of the grid encoding -> (dL_ddLdoutput, dL_dparams, dL_dinput); entries are None when the
-        corresponding tensor does not require a gradient."""
+        """Second-order pass of the grid encoding or of an fp32 network (create_network_precision) -> (dL_ddLdoutput, dL_dparams,
+        dL_dinput) in the module's own output / parameter precisions; entries are None when the corresponding tensor does not require a
+        gradient."""
         for t in (input, params, dL_ddLdinput, dL_doutput):
             if not t.is_cuda or not t.is_contiguous():
                 raise RuntimeError("bwd_bwd_input: tensors must be contiguous and on the GPU")

@@ -326,7 +326,8 @@ struct NativeBackwardFunction : public torch::autograd::Function<NativeBackwardF
 			scaled = scaled_doutput(dy, st->loss_scale, torch_type(st->module->output_precision()));
 		}
 		at::AutoGradMode no_grad(false);
-		// (a 16-bit x belongs to a bare network, whose second-order pass the library refuses as the reference does: widened so that it gets there)
+		// (a 16-bit x belongs to a bare 16-bit network, whose second-order pass the library refuses as the reference does: widened so that it
+		// gets there; an fp32 network's x is fp32 and its pass runs, with float results: the output / parameter precisions above)
 		auto r = st->module->bwd_bwd_input(st->native_ctx, x.to(torch::kFloat32), params, ddx.to(torch::kFloat32).contiguous(), scaled);
 		// d_dy depends on ddx only; the other two carry one factor of the loss scale through the scaled dL/doutput
 		torch::Tensor d_dy = std::get<0>(r) ? *std::get<0>(r) : torch::Tensor();

@@ -12,7 +12,9 @@ Behavioural contract kept from the reference:
   * native objects are not pickled; they are rebuilt from the stored configs on unpickling.
 Beyond the reference: a `Network` given an input in its own 16-bit dtype (another module's output) reads it as it is and returns a 16-bit
 input gradient; every other input is cast to fp32 as in the reference.
-Second-order gradients of the grid encoding (`bwd_bwd_input`) are available through double backward, as in the reference.
+Second-order gradients of the grid encoding (`bwd_bwd_input`) are available through double backward, as in the reference; beyond it, so
+are those of an fp32 `Network` (dtype=torch.float32): `torch.autograd.grad(..., create_graph=True)` through the MLP, for eikonal and
+curvature losses.  16-bit networks and `NetworkWithInputEncoding` raise "not implemented"; `Encoding` + `Network` in fp32 compose.
 """
 import gc
 import warnings
@@ -88,8 +90,8 @@ def _none_if_scalar(t):
 
 class _NativeBackwardFunction(torch.autograd.Function):
     """First-order backward as a differentiable op.  Its own backward is the native second-order pass
-    (`bwd_bwd_input`, reference modules.py:163-203 / grid.h:910-1042): gradients of dL_dinput with respect to
-    dL_doutput, the parameters and the input.  Gradients OF the parameter gradient are not available."""
+    (`bwd_bwd_input`, reference modules.py:163-203 / grid.h:910-1042; here also the fp32 network's): gradients of dL_dinput with
+    respect to dL_doutput, the parameters and the input.  Gradients OF the parameter gradient are not available."""
 
     @staticmethod
     def forward(ctx, fwd_ctx, dy, x, params, y):
@@ -110,7 +112,8 @@ class _NativeBackwardFunction(torch.autograd.Function):
         with torch.enable_grad():  # keeps dy's requires_grad flag (this method runs under no_grad by default)
             scaled_dy = (dy * scale).to(_precision_dtype(fwd_ctx.native_module)).contiguous()
         with torch.no_grad():
-            # (a 16-bit x belongs to a bare network, whose second-order pass the library refuses as the reference does: widened so that it gets there)
+            # (a 16-bit x belongs to a bare 16-bit network, whose second-order pass the library refuses as the reference does: widened so that
+            # it gets there; an fp32 network's x is fp32 and its pass runs)
             d_dy, d_params, d_x = fwd_ctx.native_module.bwd_bwd_input(fwd_ctx.native_ctx, x.to(torch.float), params, ddx.to(torch.float).contiguous(), scaled_dy)
             # d_dy depends on ddx only; the other two carry one factor of the loss scale through scaled_dy
             d_params = None if d_params is None else d_params / scale
