@@ -149,6 +149,9 @@ int tcnn_module_backward_half_input(tcnn_module_t* m, tcnn_stream_t stream, cons
 uint32_t tcnn_module_n_input_dims(const tcnn_module_t* m);
 uint32_t tcnn_module_n_output_dims(const tcnn_module_t* m); /* PADDED width, cpp_api.cu:137 */
 size_t tcnn_module_n_params(const tcnn_module_t* m);
+/* The weight matrices that lead the module's parameter vector, in order (what Optimizer::allocate takes as layer_sizes: Adam's matrix /
+ * non-matrix split, Novograd's per-layer norms): rows[l] x cols[l] for l < min(*n_layers, capacity).  A bare encoding has 0 layers. */
+int tcnn_module_network_layers(const tcnn_module_t* m, uint32_t* rows, uint32_t* cols, size_t capacity, size_t* n_layers);
 int tcnn_module_param_precision(const tcnn_module_t* m);
 int tcnn_module_output_precision(const tcnn_module_t* m);
 int tcnn_module_initialize_params(tcnn_module_t* m, size_t seed, float* params_full_precision, float scale);
@@ -346,12 +349,23 @@ int tcnn_optimizer_serialize(tcnn_optimizer_t* o, void* buffer, size_t capacity,
 int tcnn_optimizer_deserialize(tcnn_optimizer_t* o, const void* data, size_t n_bytes);
 void* tcnn_optimizer_custom_weights(tcnn_optimizer_t* o); /* Optimizer::custom_weights(): the outermost wrapper's inference weights, or NULL */
 void tcnn_optimizer_destroy(tcnn_optimizer_t* o);
+/* Optimizer<T> with T chosen like create_encoding's precision: the library's own 16-bit precision gives exactly tcnn_create_optimizer's
+ * object; TCNN_PRECISION_FP32 gives the reference's Optimizer<float> -- ONE float weight vector, float gradients, and float wrapper state
+ * (weights_ema, weights_lookahead, weights_samples / weights_average, averaged_gradients_half: 4 bytes per element in state_named and in
+ * snapshots); the other 16-bit type is refused.  The same chains are accepted and refused.  Every tcnn_optimizer_* entry works on it;
+ * tcnn_optimizer_step reads `gradients` as float and steps `weights_full_precision` in place, `weights` must be NULL or the same pointer. */
+int tcnn_create_optimizer_precision(const char* optimizer_json, int requested_precision, tcnn_optimizer_t** out);
+int tcnn_optimizer_precision(const tcnn_optimizer_t* o);
 /* Loss<T>::evaluate on its own (reference loss.h:42-50 and the headers under losses/): `loss_otype` as in the JSON ("RelativeL2", "L2", "L1", ...).
  * prediction / gradients: column-major `stride` x n matrices of the library's 16-bit type (stride = padded output width, a multiple of
  * 8), target / data_pdf (may be NULL): `dims` x n fp32, values (may be NULL): `stride` x n fp32.  Rows >= dims carry no loss; the
  * normalisation is n * dims as in the reference's kernels. */
 int tcnn_loss_evaluate(const char* loss_otype, tcnn_stream_t stream, uint32_t n, uint32_t stride, uint32_t dims, float loss_scale, const void* prediction,
                        const float* target, const float* data_pdf, float* values, void* gradients);
+/* tcnn_loss_evaluate with prediction / gradients in `requested_precision`: the library's 16-bit precision is tcnn_loss_evaluate itself,
+ * TCNN_PRECISION_FP32 takes float matrices (16-byte aligned) and leaves the gradient in fp32 (Loss<float>). */
+int tcnn_loss_evaluate_precision(const char* loss_otype, tcnn_stream_t stream, uint32_t n, uint32_t stride, uint32_t dims, float loss_scale, int requested_precision,
+                                 const void* prediction, const float* target, const float* data_pdf, float* values, void* gradients);
 /* Exchange overlapped with the backward pass (no reference counterpart).  `ready(user, begin, end, stream)` is called on
  * the host, inside training_step, as soon as the kernels that produce the gradients [begin, end) of the fp16 gradient buffer have been
  * enqueued on `stream`: first the network's weights [0, n_network_params), then the encoding's levels in

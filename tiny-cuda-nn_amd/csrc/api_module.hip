@@ -2,6 +2,8 @@
 #include <algorithm>
 #include <memory>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "host_common.h"
 #include "model_exec.h"
@@ -352,6 +354,25 @@ void tcnn_context_destroy(tcnn_context_t* ctx) { delete ctx; }
 uint32_t tcnn_module_n_input_dims(const tcnn_module_t* m) { return m->md.n_input_dims; }
 uint32_t tcnn_module_n_output_dims(const tcnn_module_t* m) { return m->md.padded_output_width(); }
 size_t tcnn_module_n_params(const tcnn_module_t* m) { return m->md.n_params(); }
+// the weight matrices that lead the module's parameter vector, in order (Optimizer::allocate's layer_sizes, object.h layer_sizes()): rows x
+// cols of each into rows[] / cols[] (`capacity` entries each, may be NULL with capacity 0), their number into *n_layers.  A bare encoding has none.
+int tcnn_module_network_layers(const tcnn_module_t* m, uint32_t* rows, uint32_t* cols, size_t capacity, size_t* n_layers) {
+	TCNN_API_BEGIN
+	std::vector<std::pair<uint32_t, uint32_t>> layers;
+	if (m->md.has_network) {
+		const MlpMeta& mlp = m->md.net.mlp;
+		layers.emplace_back(mlp.width, mlp.in_width);
+		for (uint32_t l = 0; l < mlp.n_hidden_matmuls; ++l) layers.emplace_back(mlp.width, mlp.width);
+		layers.emplace_back(mlp.padded_out, mlp.width);
+	}
+	if (n_layers) *n_layers = layers.size();
+	if (capacity && (!rows || !cols)) throw std::runtime_error("tcnn_module_network_layers: missing output array");
+	for (size_t l = 0; l < layers.size() && l < capacity; ++l) {
+		rows[l] = layers[l].first;
+		cols[l] = layers[l].second;
+	}
+	TCNN_API_END
+}
 int tcnn_module_param_precision(const tcnn_module_t* m) { return m->fp32_io ? TCNN_PRECISION_FP32 : NATIVE_PRECISION; }
 int tcnn_module_output_precision(const tcnn_module_t* m) { return m->fp32_io ? TCNN_PRECISION_FP32 : NATIVE_PRECISION; }
 

@@ -9,6 +9,7 @@
 #include "host_common.h"
 #include "model_desc.h"
 #include "optimizer_chain.h"
+#include "optimizer_kernels_f32.h"
 
 using namespace tcnn_hip;
 
@@ -28,6 +29,22 @@ int tcnn_create_optimizer(const char* optimizer_json, tcnn_optimizer_t** out) {
 	*out = o.release();
 	TCNN_API_END
 }
+// Optimizer<T> with T by `requested_precision`: the library's own 16-bit precision gives exactly what tcnn_create_optimizer gives;
+// TCNN_PRECISION_FP32 the reference's Optimizer<float> (optimizer_kernels_f32.h): one float weight vector, float gradients, float wrapper state
+int tcnn_create_optimizer_precision(const char* optimizer_json, int requested_precision, tcnn_optimizer_t** out) {
+	if (requested_precision == NATIVE_PRECISION) return tcnn_create_optimizer(optimizer_json, out);
+	TCNN_API_BEGIN
+	if (requested_precision != TCNN_PRECISION_FP32) {
+		set_last_error(HALF_IS_BF16 ? "create_optimizer: this build (libtcnn_hip_bf16.so) provides bf16 and fp32 optimizers, not fp16 ones"
+		                            : "create_optimizer: this build provides fp16 and fp32 optimizers, not bf16 ones");
+		return TCNN_ERROR_UNSUPPORTED;
+	}
+	auto o = std::make_unique<tcnn_optimizer>();
+	o->chain = std::make_unique<OptimizerChain>(Json::parse(optimizer_json ? optimizer_json : "{}"), /*fp32=*/true);
+	*out = o.release();
+	TCNN_API_END
+}
+int tcnn_optimizer_precision(const tcnn_optimizer_t* o) { return o->chain->fp32() ? TCNN_PRECISION_FP32 : NATIVE_PRECISION; }
 // Optimizer::allocate(n_weights, layer_sizes): the layers' weight matrices lead the parameter vector (weight decay / l2_reg of Adam apply to
 // them, adam.h:79-110; Novograd steps them alone, layer by layer), the rest (e.g. an encoding's) are no matrix weights
 int tcnn_optimizer_allocate_layers(tcnn_optimizer_t* o, size_t n_weights, size_t n_layers, const uint32_t* rows, const uint32_t* cols) {
@@ -48,8 +65,16 @@ int tcnn_optimizer_allocate(tcnn_optimizer_t* o, size_t n_weights, size_t n_matr
 int tcnn_optimizer_step(tcnn_optimizer_t* o, tcnn_stream_t stream, float loss_scale, float* weights_full_precision, void* weights, const void* gradients) {
 	TCNN_API_BEGIN
 	if (!o->chain->n_weights()) return TCNN_OK;
+	if (o->chain->fp32()) {  // one float weight vector: gradients are floats, `weights` names the same buffer or nothing
+		if (!weights_full_precision || !gradients) throw std::runtime_error("Optimizer::step: missing buffer");
+		if (weights && weights != (void*)weights_full_precision) {
+			throw std::runtime_error("Optimizer::step: an fp32 optimizer steps ONE float weight vector: `weights` must be NULL or equal to `weights_full_precision`");
+		}
+		o->chain->step((hipStream_t)stream, loss_scale, weights_full_precision, nullptr, gradients);
+		return TCNN_OK;
+	}
 	if (!weights_full_precision || !weights || !gradients) throw std::runtime_error("Optimizer::step: missing buffer");
-	o->chain->step((hipStream_t)stream, loss_scale, weights_full_precision, (half_t*)weights, (const half_t*)gradients);
+	o->chain->step((hipStream_t)stream, loss_scale, weights_full_precision, weights, gradients);
 	TCNN_API_END
 }
 uint32_t tcnn_optimizer_step_count(const tcnn_optimizer_t* o) { return o->chain->step_count(); }
@@ -124,6 +149,26 @@ int tcnn_loss_evaluate(const char* loss_otype, tcnn_stream_t stream, uint32_t n,
 	if (n == 0) return TCNN_OK;
 	loss_evaluate((hipStream_t)stream, string_to_loss(loss_otype), n, stride, dims, loss_scale, (const half_t*)prediction, target, data_pdf, values, (half_t*)gradients,
 	              nullptr, n * dims);
+	TCNN_API_END
+}
+
+// the same with prediction / gradients in `requested_precision`: the library's 16-bit one is tcnn_loss_evaluate; TCNN_PRECISION_FP32 takes
+// float matrices (Loss<float>: the same arithmetic, the gradient is not rounded to 16 bits)
+int tcnn_loss_evaluate_precision(const char* loss_otype, tcnn_stream_t stream, uint32_t n, uint32_t stride, uint32_t dims, float loss_scale, int requested_precision,
+                                 const void* prediction, const float* target, const float* data_pdf, float* values, void* gradients) {
+	if (requested_precision == NATIVE_PRECISION) return tcnn_loss_evaluate(loss_otype, stream, n, stride, dims, loss_scale, prediction, target, data_pdf, values, gradients);
+	TCNN_API_BEGIN
+	if (requested_precision != TCNN_PRECISION_FP32) {
+		set_last_error(HALF_IS_BF16 ? "Loss::evaluate: this build (libtcnn_hip_bf16.so) provides bf16 and fp32 losses, not fp16 ones"
+		                            : "Loss::evaluate: this build provides fp16 and fp32 losses, not bf16 ones");
+		return TCNN_ERROR_UNSUPPORTED;
+	}
+	if (!loss_otype || !prediction || !target || !gradients) throw std::runtime_error("Loss::evaluate: missing argument");
+	if (stride % 8 != 0 || dims > stride) throw std::runtime_error("Loss::evaluate: the prediction's row count must be a multiple of 8 and at least the target's");
+	if ((uint64_t)n * dims > 0xFFFFFFFFull || (uint64_t)n * stride > 0xFFFFFFFFull) throw std::runtime_error("Loss::evaluate: batch too large");
+	if (n == 0) return TCNN_OK;
+	loss_evaluate_f32((hipStream_t)stream, string_to_loss(loss_otype), n, stride, dims, loss_scale, (const float*)prediction, target, data_pdf, values, (float*)gradients,
+	                  n * dims);
 	TCNN_API_END
 }
 

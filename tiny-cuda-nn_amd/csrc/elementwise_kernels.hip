@@ -4,6 +4,7 @@
 #include "elementwise_kernels.h"
 #include <type_traits>
 #include "adam_device.h"
+#include "optimizer_device.h"
 #include "encoding_device.h"
 
 #include <cmath>
@@ -357,7 +358,7 @@ __global__ void __launch_bounds__(EW_THREADS) k_ema_step(uint32_t n, float ema_d
 #pragma unroll
 		for (uint32_t j = 0; j < 8; ++j) {
 			const float old = tmp ? tmp[i0 + j] : (float)e[j];
-			const float filtered = (old * ema_decay * ema_debias_old + (float)w[j] * (1 - ema_decay)) * ema_debias_new;
+			const float filtered = ema_one(old, (float)w[j], ema_decay, ema_debias_old, ema_debias_new);
 			if (tmp) tmp[i0 + j] = filtered;
 			e[j] = (half_t)filtered;
 		}
@@ -365,7 +366,7 @@ __global__ void __launch_bounds__(EW_THREADS) k_ema_step(uint32_t n, float ema_d
 	} else {
 		for (uint32_t i = i0; i < n; ++i) {
 			const float old = tmp ? tmp[i] : (float)weights_ema[i];
-			const float filtered = (old * ema_decay * ema_debias_old + (float)weights[i] * (1 - ema_decay)) * ema_debias_new;
+			const float filtered = ema_one(old, (float)weights[i], ema_decay, ema_debias_old, ema_debias_new);
 			if (tmp) tmp[i] = filtered;
 			weights_ema[i] = (half_t)filtered;
 		}

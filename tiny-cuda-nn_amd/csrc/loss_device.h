@@ -22,7 +22,9 @@ constexpr int N_LOSS_TYPES = 9;
 #else
 #define TCNN_LOSS_NOINLINE __device__ __attribute__((noinline))
 #endif
-TCNN_LOSS_NOINLINE half_t loss_element_general(LossType type, float prediction, float target, float pdf, float n_total, float loss_scale, float& value) {
+// G: the gradient's type -- half_t (the default: every 16-bit kernel), or float (Loss<float>: the same arithmetic, nothing rounded to 16 bits)
+template <typename G = half_t>
+TCNN_LOSS_NOINLINE G loss_element_general(LossType type, float prediction, float target, float pdf, float n_total, float loss_scale, float& value) {
 	const float difference = prediction - target;
 	float gradient;  // dL/dprediction before the 1 / n_total of the mean
 	switch (type) {
@@ -57,43 +59,44 @@ TCNN_LOSS_NOINLINE half_t loss_element_general(LossType type, float prediction, 
 		case LossType::CrossEntropy: {  // cross_entropy.h:66-76: the factor already holds 1 / n_total
 			const float factor = -target / pdf / n_total;
 			value = factor * logf(prediction);
-			return to_half_rn(loss_scale * (factor / prediction));
+			return round_to<G>(loss_scale * (factor / prediction));
 		}
 		case LossType::Variance: {  // variance_is.h:66-76
 			const float factor = target * target / pdf / n_total;
 			value = factor / prediction - factor / pdf;
-			return to_half_rn(loss_scale * (-factor / (prediction * prediction)));
+			return round_to<G>(loss_scale * (-factor / (prediction * prediction)));
 		}
 		default:  // L2, l2.h:69-74
 			value = difference * difference / pdf / n_total;
 			gradient = 2 * difference / pdf;
 			break;
 	}
-	return to_half_rn(loss_scale * gradient / n_total);
+	return round_to<G>(loss_scale * gradient / n_total);
 }
 
 TCNN_DEVICE float loss_row_luminance(float r, float g, float b) { return 0.299f * r + 0.587f * g + 0.114f * b; }
-TCNN_DEVICE half_t loss_element_luminance(float prediction, float luminance, float target, float pdf, float n_total, float loss_scale, float& value) {
+template <typename G = half_t>
+TCNN_DEVICE G loss_element_luminance(float prediction, float luminance, float target, float pdf, float n_total, float loss_scale, float& value) {
 	const float prediction_sq_plus_epsilon = luminance * luminance + 0.01f;
 	const float difference = prediction - target;
 	value = difference * difference / prediction_sq_plus_epsilon / pdf / n_total;
 	const float gradient = 2 * difference / prediction_sq_plus_epsilon / pdf;
-	return to_half_rn(loss_scale * gradient / n_total);
+	return round_to<G>(loss_scale * gradient / n_total);
 }
 
 // RelativeL2 / L2 (the defaults) inline, the rest through one out-of-line copy (see activation_device.h)
 TCNN_HOST_DEVICE bool loss_is_simple(LossType type) { return type == LossType::RelativeL2 || type == LossType::L2; }
 TCNN_HOST_DEVICE bool loss_is_elementwise(LossType type) { return type != LossType::RelativeL2Luminance; }
-template <bool GENERAL = true>
-TCNN_DEVICE half_t loss_element(LossType type, float prediction, float target, float pdf, float n_total, float loss_scale, float& value) {
+template <bool GENERAL = true, typename G = half_t>
+TCNN_DEVICE G loss_element(LossType type, float prediction, float target, float pdf, float n_total, float loss_scale, float& value) {
 	if (!GENERAL || type == LossType::RelativeL2 || type == LossType::L2) {
 		const float difference = prediction - target;
 		const float denom = type == LossType::RelativeL2 ? prediction * prediction + 0.01f : 1.0f;
 		value = type == LossType::RelativeL2 ? difference * difference / denom / pdf / n_total : difference * difference / pdf / n_total;
 		const float gradient = type == LossType::RelativeL2 ? 2 * difference / denom / pdf : 2 * difference / pdf;
-		return to_half_rn(loss_scale * gradient / n_total);
+		return round_to<G>(loss_scale * gradient / n_total);
 	}
-	if constexpr (GENERAL) return loss_element_general(type, prediction, target, pdf, n_total, loss_scale, value);
+	if constexpr (GENERAL) return loss_element_general<G>(type, prediction, target, pdf, n_total, loss_scale, value);
 }
 
 }  // namespace tcnn_hip

@@ -59,7 +59,7 @@ Json adam_hyperparams_json(const AdamHyper& h) {
 	return o;
 }
 
-OptimizerChain::OptimizerChain(const Json& config) {
+OptimizerChain::OptimizerChain(const Json& config, bool fp32) : m_fp32(fp32) {
 	Json cur = config;
 	for (;;) {
 		const Kind kind = kind_of(cur.value("otype", "Adam"));
@@ -273,7 +273,7 @@ uint32_t OptimizerChain::step_count(size_t d) const {
 	return 0;
 }
 
-half_t* OptimizerChain::custom_weights(size_t d) const {
+void* OptimizerChain::custom_weights(size_t d) const {
 	for (; d < m_nodes.size(); ++d) {
 		const Node& n = m_nodes[d];
 		if (n.kind == Kind::Ema) return n.weights_ema;
@@ -289,6 +289,8 @@ static T* zeroed(size_t count) {
 	HIP_CHECK(hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T)));
 	return p;
 }
+// a buffer of the chain's value type
+static void* zeroed_values(size_t count, bool fp32) { return fp32 ? (void*)zeroed<float>(count) : (void*)zeroed<half_t>(count); }
 
 void OptimizerChain::allocate_average(Node& n) {
 	(void)hipDeviceSynchronize();
@@ -296,8 +298,8 @@ void OptimizerChain::allocate_average(Node& n) {
 	device_free(n.weights_average);
 	n.weights_samples = n.weights_average = nullptr;
 	if ((uint64_t)m_n * n.n_samples > 0xFFFFFFFFull) throw std::runtime_error("Average: n_weights * n_samples exceeds 2^32 elements");
-	n.weights_samples = zeroed<half_t>((size_t)m_n * n.n_samples);
-	n.weights_average = zeroed<half_t>(m_n);
+	n.weights_samples = zeroed_values((size_t)m_n * n.n_samples, m_fp32);
+	n.weights_average = zeroed_values(m_n, m_fp32);
 }
 
 void OptimizerChain::allocate(uint32_t n_weights, const std::vector<std::pair<uint32_t, uint32_t>>& layer_sizes) {
@@ -335,35 +337,48 @@ void OptimizerChain::allocate(uint32_t n_weights, const std::vector<std::pair<ui
 				n.partials = zeroed<float>(NOVOGRAD_MAX_LAYERS * NOVOGRAD_REDUCE_BLOCKS);
 				break;
 			case Kind::Ema:  // ema.h:90-102
-				n.weights_ema = zeroed<half_t>(m_n);
-				if (n.ema_full_precision) n.ema_tmp = zeroed<float>(m_n);
+				n.weights_ema = zeroed_values(m_n, m_fp32);
+				if (n.ema_full_precision && !m_fp32) n.ema_tmp = zeroed<float>(m_n);  // (an fp32 average is its own full-precision copy)
 				break;
 			case Kind::ExponentialDecay: break;
-			case Kind::Lookahead: n.weights_lookahead = zeroed<half_t>(m_n); break;
+			case Kind::Lookahead: n.weights_lookahead = zeroed_values(m_n, m_fp32); break;
 			case Kind::Average: allocate_average(n); break;
 			case Kind::Batched:
 				n.averaged_gradients = zeroed<float>(m_n);
-				n.averaged_gradients_half = zeroed<half_t>(m_n);
+				n.averaged_gradients_half = zeroed_values(m_n, m_fp32);
 				break;
 		}
 	}
 }
 
-void OptimizerChain::step(hipStream_t stream, float loss_scale, float* master, half_t* weights, const half_t* gradients) {
+void OptimizerChain::step(hipStream_t stream, float loss_scale, float* master, void* weights, const void* gradients) {
 	if (!m_n) return;
 	step_node(0, stream, loss_scale, master, weights, gradients, 0, m_n, /*advance=*/true);
 }
 
-void OptimizerChain::step_range(hipStream_t stream, float loss_scale, float* master, half_t* weights, const half_t* gradients, uint32_t begin, uint32_t end, bool advance) {
+void OptimizerChain::step_range(hipStream_t stream, float loss_scale, float* master, void* weights, const void* gradients, uint32_t begin, uint32_t end, bool advance) {
 	if (const char* who = ranged_refusal()) {
 		throw std::runtime_error(std::string("optimizer_step_range: the ") + who + " optimizer cannot step a range of the parameters (it needs the whole gradient in one call)");
 	}
 	step_node(0, stream, loss_scale, master, weights, gradients, begin, std::min(end, m_n), advance);
 }
 
-void OptimizerChain::step_node(size_t d, hipStream_t stream, float loss_scale, float* master, half_t* weights, const half_t* gradients, uint32_t begin, uint32_t end,
+// exponential_decay.h:59-70, step() == the nested count before this step
+void OptimizerChain::advance_exponential_decay(size_t d) {
+	Node& n = m_nodes[d];
+	const uint32_t step = step_count(d + 1);
+	if (step == 0) n.lr_factor = 1.0f;
+	if (step >= n.decay_start && (step - n.decay_start) % n.decay_interval == 0 && step <= n.decay_end) n.lr_factor *= n.decay_base;
+	Node& b = m_nodes.back();
+	(b.kind == Kind::Adam ? b.adam.learning_rate : b.kind == Kind::SGD ? b.sgd_learning_rate : b.novograd.learning_rate) = n.base_lr * n.lr_factor;
+}
+
+void OptimizerChain::step_node(size_t d, hipStream_t stream, float loss_scale, float* master, void* weights_v, const void* gradients_v, uint32_t begin, uint32_t end,
                                bool advance) {
 	Node& n = m_nodes[d];
+	if (m_fp32) return step_node_f32(d, stream, loss_scale, master, (const float*)gradients_v, begin, end, advance);
+	half_t* weights = (half_t*)weights_v;
+	const half_t* gradients = (const half_t*)gradients_v;
 	switch (n.kind) {
 		case Kind::Adam:
 			if (advance) ++n.current_step;  // adam.h:159
@@ -382,37 +397,81 @@ void OptimizerChain::step_node(size_t d, hipStream_t stream, float loss_scale, f
 		}
 		case Kind::Ema: {  // ema.h:102-136
 			step_node(d + 1, stream, loss_scale, master, weights, gradients, begin, end, advance);
-			const half_t* nested_custom = custom_weights(d + 1);
-			ema_step(stream, m_n, n.ema_decay, step_count(d + 1), nested_custom ? nested_custom : weights, n.weights_ema, n.ema_tmp, begin, end);
+			const half_t* nested_custom = (const half_t*)custom_weights(d + 1);
+			ema_step(stream, m_n, n.ema_decay, step_count(d + 1), nested_custom ? nested_custom : weights, (half_t*)n.weights_ema, n.ema_tmp, begin, end);
 			break;
 		}
 		case Kind::ExponentialDecay:  // exponential_decay.h:59-70, step() == the nested count before this step
-			if (advance) {
-				const uint32_t step = step_count(d + 1);
-				if (step == 0) n.lr_factor = 1.0f;
-				if (step >= n.decay_start && (step - n.decay_start) % n.decay_interval == 0 && step <= n.decay_end) n.lr_factor *= n.decay_base;
-				Node& b = m_nodes.back();
-				(b.kind == Kind::Adam ? b.adam.learning_rate : b.kind == Kind::SGD ? b.sgd_learning_rate : b.novograd.learning_rate) = n.base_lr * n.lr_factor;
-			}
+			if (advance) advance_exponential_decay(d);
 			step_node(d + 1, stream, loss_scale, master, weights, gradients, begin, end, advance);
 			break;
 		case Kind::Lookahead: {  // lookahead.h:78-96; the copy is ordered on the stream (the step may be under graph capture)
 			const uint32_t current = step_count(d + 1);
 			if (current == 0) HIP_CHECK(hipMemcpyAsync(n.weights_lookahead, weights, (size_t)m_n * sizeof(half_t), hipMemcpyDeviceToDevice, stream));
-			if (current % n.n_steps == 0) lookahead_step(stream, m_n, n.alpha, master, weights, n.weights_lookahead);
+			if (current % n.n_steps == 0) lookahead_step(stream, m_n, n.alpha, master, weights, (half_t*)n.weights_lookahead);
 			step_node(d + 1, stream, loss_scale, master, weights, gradients, begin, end, advance);
 			break;
 		}
 		case Kind::Average:  // average.h:81-91, slot = step() % n_samples AFTER the nested step
 			step_node(d + 1, stream, loss_scale, master, weights, gradients, begin, end, advance);
-			average_step(stream, m_n, n.n_samples, weights, n.weights_samples + (size_t)(step_count(d + 1) % n.n_samples) * m_n, n.weights_average);
+			average_step(stream, m_n, n.n_samples, weights, (half_t*)n.weights_samples + (size_t)(step_count(d + 1) % n.n_samples) * m_n, (half_t*)n.weights_average);
 			break;
 		case Kind::Batched:  // batched.h:78-89
 			batched_accumulate(stream, m_n, n.current_step % n.batch_size_multiplier == 0, n.batch_size_multiplier, gradients, n.averaged_gradients);
 			++n.current_step;
 			if (n.current_step % n.batch_size_multiplier == 0) {
-				batched_cast(stream, m_n, n.averaged_gradients, n.averaged_gradients_half);
+				batched_cast(stream, m_n, n.averaged_gradients, (half_t*)n.averaged_gradients_half);
 				step_node(d + 1, stream, loss_scale, master, weights, n.averaged_gradients_half, begin, end, advance);
+			}
+			break;
+	}
+}
+
+// the same host logic for a chain over float: ONE weight vector (`weights`), float gradients, float wrapper state
+void OptimizerChain::step_node_f32(size_t d, hipStream_t stream, float loss_scale, float* weights, const float* gradients, uint32_t begin, uint32_t end, bool advance) {
+	Node& n = m_nodes[d];
+	switch (n.kind) {
+		case Kind::Adam:
+			if (advance) ++n.current_step;  // adam.h:159
+			adam_step_f32(stream, n.adam, m_n, m_n_matrix, loss_scale, n.current_step, weights, gradients, n.m1, n.m2, n.param_steps, begin, end);
+			break;
+		case Kind::SGD:
+			if (advance) ++n.current_step;  // sgd.h:82
+			sgd_step_f32(stream, m_n, loss_scale, n.sgd_learning_rate, n.sgd_l2_reg, weights, gradients, begin, end);
+			break;
+		case Kind::Novograd: {
+			++n.current_step;  // novograd.h:122
+			const float* in = n.layer_moments + ((n.current_step - 1u) & 1u) * NOVOGRAD_MAX_LAYERS;
+			novograd_step_f32(stream, m_layers, n.novograd, loss_scale, n.current_step == 1, weights, gradients, n.m1, in, novograd_moments(n), n.partials);
+			break;
+		}
+		case Kind::Ema: {  // ema.h:102-136
+			step_node_f32(d + 1, stream, loss_scale, weights, gradients, begin, end, advance);
+			const float* nested_custom = (const float*)custom_weights(d + 1);
+			ema_step_f32(stream, m_n, n.ema_decay, step_count(d + 1), nested_custom ? nested_custom : weights, (float*)n.weights_ema, begin, end);
+			break;
+		}
+		case Kind::ExponentialDecay:
+			if (advance) advance_exponential_decay(d);
+			step_node_f32(d + 1, stream, loss_scale, weights, gradients, begin, end, advance);
+			break;
+		case Kind::Lookahead: {  // lookahead.h:78-96
+			const uint32_t current = step_count(d + 1);
+			if (current == 0) HIP_CHECK(hipMemcpyAsync(n.weights_lookahead, weights, (size_t)m_n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+			if (current % n.n_steps == 0) lookahead_step_f32(stream, m_n, n.alpha, weights, (float*)n.weights_lookahead);
+			step_node_f32(d + 1, stream, loss_scale, weights, gradients, begin, end, advance);
+			break;
+		}
+		case Kind::Average:  // average.h:81-91, slot = step() % n_samples AFTER the nested step
+			step_node_f32(d + 1, stream, loss_scale, weights, gradients, begin, end, advance);
+			average_step_f32(stream, m_n, n.n_samples, weights, (float*)n.weights_samples + (size_t)(step_count(d + 1) % n.n_samples) * m_n, (float*)n.weights_average);
+			break;
+		case Kind::Batched:  // batched.h:78-89
+			batched_accumulate_f32(stream, m_n, n.current_step % n.batch_size_multiplier == 0, n.batch_size_multiplier, gradients, n.averaged_gradients);
+			++n.current_step;
+			if (n.current_step % n.batch_size_multiplier == 0) {
+				batched_cast_f32(stream, m_n, n.averaged_gradients, (float*)n.averaged_gradients_half);
+				step_node_f32(d + 1, stream, loss_scale, weights, (const float*)n.averaged_gradients_half, begin, end, advance);
 			}
 			break;
 	}
@@ -437,18 +496,18 @@ bool OptimizerChain::state_named(const std::string& name, void** ptr, size_t* co
 				if (name == "per_layer_second_moments") return give(n.layer_moments ? novograd_moments(n) : nullptr, m_layers.n_layers, 4);
 				break;
 			case Kind::Ema:
-				if (name == "weights_ema") return give(n.weights_ema, m_n, 2);
+				if (name == "weights_ema") return give(n.weights_ema, m_n, value_bytes());
 				break;
 			case Kind::Lookahead:
-				if (name == "weights_lookahead") return give(n.weights_lookahead, m_n, 2);
+				if (name == "weights_lookahead") return give(n.weights_lookahead, m_n, value_bytes());
 				break;
 			case Kind::Average:
-				if (name == "weights_samples") return give(n.weights_samples, (size_t)m_n * n.n_samples, 2);
-				if (name == "weights_average") return give(n.weights_average, m_n, 2);
+				if (name == "weights_samples") return give(n.weights_samples, (size_t)m_n * n.n_samples, value_bytes());
+				if (name == "weights_average") return give(n.weights_average, m_n, value_bytes());
 				break;
 			case Kind::Batched:
 				if (name == "averaged_gradients") return give(n.averaged_gradients, m_n, 4);
-				if (name == "averaged_gradients_half") return give(n.averaged_gradients_half, m_n, 2);
+				if (name == "averaged_gradients_half") return give(n.averaged_gradients_half, m_n, value_bytes());
 				break;
 			default: break;
 		}
@@ -475,7 +534,7 @@ static void read_device_blob(msgpack_detail::Reader& r, void* device, size_t byt
 
 void OptimizerChain::write_state(msgpack_detail::Writer& w, size_t d) const {
 	const Node& n = m_nodes[d];
-	const size_t nh = (size_t)m_n * sizeof(half_t), nf = (size_t)m_n * sizeof(float);
+	const size_t nh = (size_t)m_n * value_bytes(), nf = (size_t)m_n * sizeof(float);  // nh: a buffer of the value type
 	switch (n.kind) {
 		case Kind::Adam:  // adam.h:304-312
 			w.map(5);
@@ -531,7 +590,7 @@ void OptimizerChain::write_state(msgpack_detail::Writer& w, size_t d) const {
 
 void OptimizerChain::read_state(msgpack_detail::Reader& r, size_t d) {
 	Node& n = m_nodes[d];
-	const size_t nh = (size_t)m_n * sizeof(half_t), nf = (size_t)m_n * sizeof(float);
+	const size_t nh = (size_t)m_n * value_bytes(), nf = (size_t)m_n * sizeof(float);  // nh: a buffer of the value type
 	bool have_param_steps = false;
 	for (uint32_t k = 0, m = r.map_header(); k < m; ++k) {
 		const std::string key = r.str();
@@ -554,7 +613,7 @@ void OptimizerChain::read_state(msgpack_detail::Reader& r, size_t d) {
 		}
 		else if (key == "weights_ema_binary" && n.kind == Kind::Ema) {
 			read_device_blob(r, n.weights_ema, nh, "weights_ema");
-			if (n.ema_tmp) cast_f16_to_f32(nullptr, m_n, n.weights_ema, n.ema_tmp);  // ema.h:200-203
+			if (n.ema_tmp) cast_f16_to_f32(nullptr, m_n, (const half_t*)n.weights_ema, n.ema_tmp);  // ema.h:200-203
 		}
 		else if (key == "weights_lookahead_binary" && n.kind == Kind::Lookahead) read_device_blob(r, n.weights_lookahead, nh, "weights_lookahead");
 		else if (key == "weights_average_binary" && n.kind == Kind::Average) read_device_blob(r, n.weights_average, nh, "weights_average");

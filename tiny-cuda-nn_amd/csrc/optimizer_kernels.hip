@@ -4,6 +4,7 @@
 // (a ring slot of the Average optimizer when the parameter count is no multiple of 8) take the scalar form of the same arithmetic.
 // Build with -ffp-contract=off: every operation rounds as written.
 #include "optimizer_kernels.h"
+#include "optimizer_device.h"
 
 #include <stdexcept>
 #include <string>
@@ -40,11 +41,6 @@ static bool clamp_range(const char* what, uint32_t n, uint32_t& begin, uint32_t&
 static dim3 range_grid(uint32_t begin, uint32_t end) { return dim3(div_round_up(div_round_up(end - begin, OK_PER_LANE), OK_THREADS)); }
 
 // ------------------------------------------------------------------------------------------ SGD
-TCNN_DEVICE float sgd_one(float loss_scale, float learning_rate, float l2_reg, float weight_fp, half_t gradient_raw) {  // sgd.h:57-65
-	float gradient = (float)gradient_raw / loss_scale;
-	gradient += l2_reg * weight_fp;
-	return weight_fp - learning_rate * gradient;
-}
 __global__ void __launch_bounds__(OK_THREADS) k_sgd_step(uint32_t begin, uint32_t end, uint32_t vec, float loss_scale, float learning_rate, float l2_reg,
                                                           float* __restrict__ weights_fp32, half_t* __restrict__ weights, const half_t* __restrict__ gradients) {
 	const uint32_t i0 = begin + (blockIdx.x * OK_THREADS + threadIdx.x) * OK_PER_LANE;
@@ -104,17 +100,6 @@ __global__ void __launch_bounds__(OK_THREADS) k_novograd_reduce(const NovogradLa
 	if (threadIdx.x == 0) partials[layer * NOVOGRAD_REDUCE_BLOCKS + blockIdx.x] = red[0];
 }
 
-struct NovogradArgs {
-	float relative_weight_decay, absolute_weight_decay, loss_scale, learning_rate, beta1, beta2, epsilon;
-};
-// novograd.h:62-69 with the layer's second moment in a register
-TCNN_DEVICE float novograd_one(const NovogradArgs& a, float second_moment, float weight_fp, half_t gradient_raw, float& first_moment) {
-	const float gradient = (float)gradient_raw / a.loss_scale;
-	first_moment = a.beta1 * first_moment + (1 - a.beta1) * gradient / (__builtin_sqrtf(second_moment) + a.epsilon);
-	const float rel = a.relative_weight_decay * a.learning_rate, ab = a.absolute_weight_decay * a.learning_rate;
-	const float decayed_weight = (1 - rel) * weight_fp - __builtin_copysignf(ab, weight_fp);  // common_device.h:1045-1048 weight_decay
-	return decayed_weight - a.learning_rate * first_moment;
-}
 // (2) the step of every layer: workgroups [block_begin[l], block_begin[l + 1]) work on layer l
 __global__ void __launch_bounds__(OK_THREADS) k_novograd_step(const NovogradLayers layers, const NovogradArgs a, uint32_t vec, float* __restrict__ weights_fp32,
                                                                half_t* __restrict__ weights, const half_t* __restrict__ gradients, float* __restrict__ first_moments,
@@ -127,7 +112,7 @@ __global__ void __launch_bounds__(OK_THREADS) k_novograd_step(const NovogradLaye
 	// the layer's squared gradient norm: its partial sums in index order; then novograd.h:84
 	float gradient_norm = 0.0f;
 	for (uint32_t x = 0; x < NOVOGRAD_REDUCE_BLOCKS; ++x) gradient_norm += partials[layer * NOVOGRAD_REDUCE_BLOCKS + x];
-	const float second_moment = a.beta2 * second_moments_in[layer] + (1 - a.beta2) * gradient_norm / a.loss_scale / a.loss_scale;
+	const float second_moment = novograd_second_moment(a, second_moments_in[layer], gradient_norm);
 	if (local_block == 0 && threadIdx.x == 0) second_moments_out[layer] = second_moment;
 
 	const uint32_t i0 = layer_begin + (local_block * OK_THREADS + threadIdx.x) * OK_PER_LANE;
@@ -176,7 +161,6 @@ void novograd_step(hipStream_t stream, NovogradLayers layers, const NovogradHype
 }
 
 // ------------------------------------------------------------------------------------------ Lookahead
-TCNN_DEVICE float lookahead_one(float alpha, half_t slow, float weight_fp) { return (float)slow * (1.0f - alpha) + weight_fp * alpha; }  // lookahead.h:55
 __global__ void __launch_bounds__(OK_THREADS) k_lookahead_step(uint32_t begin, uint32_t end, uint32_t vec, float alpha, float* __restrict__ weights_fp32,
                                                                 half_t* __restrict__ weights, half_t* __restrict__ weights_lookahead) {
 	const uint32_t i0 = begin + (blockIdx.x * OK_THREADS + threadIdx.x) * OK_PER_LANE;
@@ -207,9 +191,6 @@ void lookahead_step(hipStream_t stream, uint32_t n, float alpha, float* weights_
 }
 
 // ------------------------------------------------------------------------------------------ Average
-TCNN_DEVICE half_t average_one(float n_samples, half_t average, half_t weight, half_t sample) {  // average.h:56
-	return to_half_rn((float)average + ((float)weight - (float)sample) / n_samples);
-}
 __global__ void __launch_bounds__(OK_THREADS) k_average_step(uint32_t begin, uint32_t end, uint32_t vec, uint32_t n_samples, const half_t* __restrict__ weights,
                                                               half_t* __restrict__ weights_current_sample, half_t* __restrict__ weights_average) {
 	const uint32_t i0 = begin + (blockIdx.x * OK_THREADS + threadIdx.x) * OK_PER_LANE;
@@ -249,12 +230,12 @@ __global__ void __launch_bounds__(OK_THREADS) k_batched_accumulate(uint32_t begi
 		f8 p = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};  // batched.h:56-58
 		if (!first) p = load_f8(pool + i0);
 #pragma unroll
-		for (uint32_t j = 0; j < OK_PER_LANE; ++j) p[j] += (float)g[j] / multiplier;
+		for (uint32_t j = 0; j < OK_PER_LANE; ++j) p[j] = batched_one(p[j], g[j], multiplier);
 		store_f8(pool + i0, p);
 	} else {
 		for (uint32_t i = i0; i < min(i0 + OK_PER_LANE, end); ++i) {
 			float p = first ? 0.0f : pool[i];
-			p += (float)gradients[i] / multiplier;
+			p = batched_one(p, gradients[i], multiplier);
 			pool[i] = p;
 		}
 	}

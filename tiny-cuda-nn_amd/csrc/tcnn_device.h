@@ -230,6 +230,16 @@ TCNN_DEVICE half_t to_half_rn(float x) {
 }
 #endif
 
+// an fp32 result as the value type T of a kernel written over it: the one extra rounding for the 16-bit type, the identity for float
+template <typename T>
+TCNN_DEVICE T round_to(float x) {
+	if constexpr (sizeof(T) == sizeof(float)) {
+		return x;
+	} else {
+		return to_half_rn(x);
+	}
+}
+
 template <typename T>
 TCNN_HOST_DEVICE T div_round_up(T a, T b) { return (a + b - 1) / b; }
 template <typename T>

@@ -42,7 +42,7 @@ struct Trainer {
 	// 16-bit gradients and leaves `params_t` stale.  Ranged stepping: OptimizerChain::ranged_refusal.
 	std::unique_ptr<OptimizerChain> chain;
 	half_t* inference_params() const {  // trainer.h:497-500: the optimizer's custom_weights() if it has any
-		if (chain) return chain->custom_weights() ? chain->custom_weights() : params;
+		if (chain) return chain->custom_weights() ? (half_t*)chain->custom_weights() : params;
 		return ema ? params_ema : params;
 	}
 	bool has_custom_weights() const { return chain ? chain->custom_weights() != nullptr : ema; }

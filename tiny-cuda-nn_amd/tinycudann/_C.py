@@ -103,6 +103,10 @@ _sig("tcnn_optimizer_custom_weights", _vp, _vp)
 _sig("tcnn_optimizer_serialize", _i, _vp, _vp, _sz, C.POINTER(_sz))
 _sig("tcnn_optimizer_deserialize", _i, _vp, _cp, _sz)
 _sig("tcnn_loss_evaluate", _i, C.c_char_p, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _f, _vp, _vp, _vp, _vp, _vp)
+_sig("tcnn_create_optimizer_precision", _i, C.c_char_p, _i, C.POINTER(_vp))
+_sig("tcnn_optimizer_precision", _i, _vp)
+_sig("tcnn_loss_evaluate_precision", _i, C.c_char_p, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _f, _i, _vp, _vp, _vp, _vp, _vp)
+_sig("tcnn_module_network_layers", _i, _vp, C.POINTER(_u32), C.POINTER(_u32), _sz, C.POINTER(_sz))
 _sig("tcnn_create_network_with_input_encoding", _i, _u32, _u32, _cp, _cp, C.POINTER(_vp))
 _sig("tcnn_create_network", _i, _u32, _u32, _cp, C.POINTER(_vp))
 _sig("tcnn_create_encoding", _i, _u32, _cp, _i, C.POINTER(_vp))
@@ -327,12 +331,17 @@ def set_grid_owner_mode(mode):
 
 
 def loss_evaluate(otype, prediction, target, loss_scale=128.0, data_pdf=None, want_values=True):
-    """Loss<T>::evaluate (loss.h:42-50) on its own.  prediction: [n][padded width] in the library's 16-bit type, target (data_pdf):
-    [n][dims] fp32 -> (values [n][padded width] fp32 or None, gradients like prediction)."""
+    """Loss<T>::evaluate (loss.h:42-50) on its own.  prediction: [n][padded width] in the library's 16-bit type or float32 (the fp32
+    kernel, tcnn_loss_evaluate_precision), target (data_pdf): [n][dims] fp32 -> (values [n][padded width] fp32 or None, gradients like
+    prediction)."""
     import torch
     n, stride = prediction.shape
     gradients = torch.empty_like(prediction)
     values = torch.empty((n, stride), dtype=torch.float32, device=prediction.device) if want_values else None
+    if prediction.dtype == torch.float32:
+        _check(_lib.tcnn_loss_evaluate_precision(str(otype).encode(), _stream(), n, stride, target.shape[1], float(loss_scale), int(Precision.Fp32), _ptr(prediction),
+                                                 _ptr(target), _ptr(data_pdf), _ptr(values), _ptr(gradients)))
+        return values, gradients
     _check(_lib.tcnn_loss_evaluate(str(otype).encode(), _stream(), n, stride, target.shape[1], float(loss_scale), _ptr(prediction), _ptr(target), _ptr(data_pdf),
                                    _ptr(values), _ptr(gradients)))
     return values, gradients
@@ -645,6 +654,14 @@ class Module:
             raise RuntimeError("set_max_level_gpu: expected a contiguous one-dimensional float32 GPU tensor")
         _check(_lib.tcnn_module_set_max_level_gpu(self._h, _ptr(values)))
 
+    def network_layers(self):
+        """(rows, cols) of the weight matrices that lead the parameter vector, in order (Optimizer::allocate's layer_sizes); [] for a bare encoding."""
+        n = C.c_size_t(0)
+        _check(_lib.tcnn_module_network_layers(self._h, None, None, 0, C.byref(n)))
+        rows, cols = (C.c_uint32 * max(n.value, 1))(), (C.c_uint32 * max(n.value, 1))()
+        _check(_lib.tcnn_module_network_layers(self._h, rows, cols, n.value, C.byref(n)))
+        return [(int(rows[l]), int(cols[l])) for l in range(n.value)]
+
     def nested_layout(self):
         """The nested encodings of a Composite, in order (empty for every other module): where each reads its input dims, writes its rows of the
         (unreduced) encoded matrix and keeps its parameters."""
@@ -716,6 +733,7 @@ class ExtModule:
     grid_level_n_params = Module.grid_level_n_params
     grid_level_params_offset = Module.grid_level_params_offset
     nested_layout = Module.nested_layout
+    network_layers = Module.network_layers
     bwd_into = Module.bwd_into
     inference_into = Module.inference_into
 

@@ -46,12 +46,18 @@ class Optimizer:
     """Optimizer<T> on its own (optimizer.h:40-99; tcnn_create_optimizer) over weight tensors the caller owns: any order of the wrappers
     Ema, ExponentialDecay, Lookahead, Average, Batched (each at most once) around one base out of Adam, SGD, Novograd.  `layer_sizes`:
     (rows, cols) of the weight matrices that lead the parameter vector (Adam's weight decay / l2_reg apply to them, adam.h:79-110; Novograd
-    steps them alone); `n_matrix_weights` alone means one such layer.  n_weights = 0 builds the optimizer without allocating anything."""
+    steps them alone); `n_matrix_weights` alone means one such layer.  n_weights = 0 builds the optimizer without allocating anything.
+    `precision`: None / the library's 16-bit precision (fp32 master weights + 16-bit weights and gradients), or _C.Precision.Fp32
+    (Optimizer<float>, tcnn_create_optimizer_precision): ONE float32 weight tensor, float32 gradients, float32 wrapper state."""
 
-    def __init__(self, config, n_weights, n_matrix_weights=0, layer_sizes=None):
+    def __init__(self, config, n_weights, n_matrix_weights=0, layer_sizes=None, precision=None):
         h = C.c_void_p()
-        _check(_lib.tcnn_create_optimizer(json.dumps(config).encode(), C.byref(h)))
+        if precision is None:
+            _check(_lib.tcnn_create_optimizer(json.dumps(config).encode(), C.byref(h)))
+        else:
+            _check(_lib.tcnn_create_optimizer_precision(json.dumps(config).encode(), int(precision), C.byref(h)))
         self._h = h
+        self.precision = _C.Precision(_lib.tcnn_optimizer_precision(h))
         self.n = int(n_weights)
         if layer_sizes is not None:
             rows = (C.c_uint32 * len(layer_sizes))(*[int(r) for r, _ in layer_sizes])
@@ -73,15 +79,40 @@ class Optimizer:
         """Optimizer::custom_weights(): the outermost wrapper's inference weights (Ema's average, Lookahead's slow weights, Average's mean)
         as a zero-copy view, or None."""
         ptr = _lib.tcnn_optimizer_custom_weights(self._h)
+        if ptr and self.precision == _C.Precision.Fp32:
+            return torch.as_tensor(_DeviceView(ptr, self.n, "<f4", self), device="cuda")
         return _half_tensor(ptr, self.n, self) if ptr else None
 
     def step(self, weights_full_precision, weights, gradients, loss_scale=128.0):
-        """weights_full_precision fp32, weights / gradients in the library's 16-bit type (gradients scaled by loss_scale)."""
-        assert weights_full_precision.numel() == weights.numel() == gradients.numel() == self.n
+        """weights_full_precision fp32, weights / gradients in the library's 16-bit type (gradients scaled by loss_scale).  An fp32
+        optimizer: step(weights, None, gradients, loss_scale) with float32 gradients; the weights are stepped in place."""
+        if self.precision == _C.Precision.Fp32:
+            assert weights_full_precision.numel() == gradients.numel() == self.n
+            for name, t in (("weights", weights_full_precision), ("gradients", gradients)):
+                if not t.is_cuda:
+                    raise RuntimeError(f"Optimizer.step: {name} must live on the GPU")
+                if t.dtype != torch.float32:
+                    raise RuntimeError(f"Optimizer.step: {name} must be float32 for an fp32 optimizer")
+                if not t.is_contiguous():
+                    raise RuntimeError(f"Optimizer.step: {name} must be contiguous")
+        else:
+            assert weights_full_precision.numel() == weights.numel() == gradients.numel() == self.n
         _check(_lib.tcnn_optimizer_step(self._h, _stream(), float(loss_scale), _ptr(weights_full_precision), _ptr(weights), _ptr(gradients)))
 
     def update_hyperparams(self, config):
         _check(_lib.tcnn_optimizer_update_hyperparams(self._h, json.dumps(config).encode()))
+
+    def serialize(self):
+        """Optimizer::serialize(): the state as MessagePack bytes (tcnn_optimizer_serialize)"""
+        n = C.c_size_t(0)
+        _check(_lib.tcnn_optimizer_serialize(self._h, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        _check(_lib.tcnn_optimizer_serialize(self._h, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def deserialize(self, data):
+        data = bytes(data)
+        _check(_lib.tcnn_optimizer_deserialize(self._h, data, len(data)))
 
     @property
     def step_count(self):
