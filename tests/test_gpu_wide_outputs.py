@@ -209,14 +209,14 @@ def test_snapshot_round_trip_resumes_training_bit_exactly():
 def test_torch_network_with_256_outputs_over_changing_batch_sizes():
     """The network of the reference's scripts/test_random_input.py -- tcnn.Network(3 -> 256, FullyFusedMLP, 128 neurons x 8 hidden layers) --
     through autograd at a fixed list of row counts, multiples of 256 and not, with the temporary memory freed in between.  One pass over
-    the list, nothing is repeated."""
+    the list; then the first row count once more on its original input, which must give the first pass's bits."""
     T = tcnn()
     net = T.Network(3, 256, network("FullyFusedMLP", 128, 8), seed=42)
     assert net.native_tcnn_module.hyperparams()["network"]["otype"] == "CutlassMLP"
     om = O.mlp_init(16, 128, 256, 8)
     assert net.params.numel() == om.n_params
     rng = np.random.default_rng(8)
-    xin = y = None
+    xin = y = first = None
     for rows in (200, 1000, 257, 1024, 999, 256, 513, 768):
         net.params.grad = None
         xin = rng.random((rows, 3), dtype=np.float32)
@@ -226,7 +226,18 @@ def test_torch_network_with_256_outputs_over_changing_batch_sizes():
         y.mean().backward()
         g = net.params.grad
         assert g is not None and g.shape == net.params.shape and torch.isfinite(g).all() and g.abs().sum() > 0
+        if first is None:
+            first = (xin, h_np(y).copy(), g.detach().cpu().numpy().copy())
         T.free_temporary_memory()
+    # the first row count once more, on its original input, after the seven other row counts: the kernels are deterministic
+    # (test_backward_is_deterministic), so the same bits (histories on recycled blocks: tests/test_gpu_call_history.py)
+    net.params.grad = None
+    again = net(torch.from_numpy(first[0]).cuda())
+    again.mean().backward()
+    g_again = net.params.grad.detach().cpu().numpy()
+    raw = lambda a: a.view(np.uint32 if a.dtype == np.float32 else np.uint16)  # noqa: E731  (the array's bits)
+    differing = int(np.count_nonzero(h_np(again) != first[1])), int(np.count_nonzero(raw(g_again) != raw(first[2])))
+    assert differing == (0, 0), f"200 rows again after the other row counts: {differing[0]} output entries and {differing[1]} parameter gradient entries differ"
     ph = O.f2h(net.params.detach().float().cpu().numpy())
     n_pad = (xin.shape[0] + 255) // 256 * 256
     xp = np.zeros((n_pad, 3), np.float32)
