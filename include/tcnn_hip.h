@@ -84,7 +84,8 @@ int tcnn_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const cha
 int tcnn_create_encoding(uint32_t n_input_dims, const char* encoding_json, int requested_precision, tcnn_module_t** out);
 /* The two network factories with create_encoding's `requested_precision`.  The library's own 16-bit precision (tcnn_preferred_precision())
  * returns exactly what the factories above return.  TCNN_PRECISION_FP32 makes an fp32 network: weights, activations, outputs, dL_dinput and
- * weight gradients are float and every product runs on the fp32 MFMA (csrc/mlp_general_fp32.hip) -- what the reference built without half
+ * weight gradients are float and every product runs on the fp32 MFMA (csrc/mlp_general_fp32.hip; forward and inference at 16 / 32 / 64
+ * neurons: the fused kernel of csrc/mlp_f32_fused.hip, see tcnn_set_fp32_fused_network) -- what the reference built without half
  * precision makes of every network (network_precision_t = float, network.cu:51-138), here a per-module choice.  Such a network is the
  * layer-by-layer one under every `otype` spelling and reports "otype": "CutlassMLP": hidden widths that are multiples of 16 up to 1024,
  * input widths (the padded encoding) multiples of 16 up to 1024, up to 1024 padded outputs, any depth >= 1 hidden layer, all ten hidden
@@ -472,6 +473,17 @@ int tcnn_get_grid_backward_mode(void);
  * bits, results widened; its parameter scatter is the bucketed pass -- A/B timing, tests).  Other modules are not affected. */
 int tcnn_set_fp32_second_order(int mode);
 int tcnn_get_fp32_second_order(void);
+/* Forward and inference of an fp32 network (tcnn_create_network[_with_input_encoding]_precision with TCNN_PRECISION_FP32), process-wide,
+ * default 1: networks with 16, 32 or 64 neurons, a (padded) input width up to 128 and up to 64 padded outputs -- any depth, any activation,
+ * any batch the module accepts -- run inference, inference into the caller's matrix and the forward pass that saves activations as ONE fused
+ * kernel (csrc/mlp_f32_fused.hip): hidden activations stay in registers and reach memory only as the saved stack that backward and
+ * backward_backward_input read, which are unchanged.  0: one launch per layer at every shape, as before the kernel existed.  The two sum
+ * over the inputs of a layer in different orders: results agree to fp32 rounding (bit for bit where every sum is exact), hyperparams() and
+ * every refusal are the same.  tcnn_module_fp32_fused_network: 1 if a forward / inference call of n_elements on this module would run the
+ * fused kernel now; 0 for 16-bit modules, bare encodings, other shapes and with the switch off. */
+int tcnn_set_fp32_fused_network(int enable);
+int tcnn_get_fp32_fused_network(void);
+int tcnn_module_fp32_fused_network(const tcnn_module_t* m, uint32_t n_elements);
 /* Accumulator form of the bucket owners in mode 3, process-wide (same bits from all three): 0 = packed (default: both features of a
  * payload word in one 64-bit LDS word, half the LDS atomics and half the LDS; slices whose sums could leave int32 are redone wide),
  * 1 = 64-bit fixed point per value throughout, 2 = the packed kernel with every slice through its wide redo (tests). */

@@ -149,6 +149,8 @@ public:
 	// library's 16-bit type, for the modules create_network makes; every other module throws.  A Context of forward_half_input goes to
 	// backward_half_input, one of forward() to backward().
 	bool supports_half_input() const { return tcnn_module_supports_half_input(m_) != 0; }
+	// Beyond the reference: would a forward / inference call of n_elements run the fused fp32 network kernel now (tcnn_set_fp32_fused_network)
+	bool fp32_fused_network(uint32_t n_elements) const { return tcnn_module_fp32_fused_network(m_, n_elements) != 0; }
 	void inference_half_input(hipStream_t stream, uint32_t n_elements, const void* input, void* output, void* params) {
 		check(tcnn_module_inference_half_input(m_, stream, n_elements, input, output, params));
 	}

@@ -8,7 +8,13 @@ the FUSED one (the JSON says which `otype` was timed); --activation SiLU makes b
 HIP events around --steps calls after --warmup calls, repeated --repeats times: the median of the repeats is reported with their minimum
 and maximum (the spread).  Buffers are allocated once, outside the timed region.
 
-usage: python scripts/time_f32_network.py [--steps 50] [--warmup 10] [--repeats 5] [--n 262144] [--activation ReLU] [--out results.json]"""
+--fused-ab: instead, the fp32 network's fused forward / inference kernel (csrc/mlp_f32_fused.hip) against the layer-by-layer kernels in the
+same run, toggled by tcnn_set_fp32_fused_network: 64 -> 64 x 2 -> 16 and 32 -> 32 x 3 -> 32, inference and the forward pass that saves
+activations (no backward).  The two settings alternate block by block (--repeats blocks of --steps calls each, after --warmup calls of
+both); per setting the median block with the minimum and maximum.  Beside each: the bytes per sample the pass has to move (input, output,
+saved activations) and the fraction of the HBM roof the median implies.
+
+usage: python scripts/time_f32_network.py [--steps 50] [--warmup 10] [--repeats 5] [--n 262144] [--activation ReLU] [--fused-ab] [--out results.json]"""
 import argparse
 import json
 import os
@@ -20,6 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, "tiny-cuda-nn_amd"))
 
 PEAK_FP32_MFMA = 157.3e12  # dense FLOP/s of v_mfma_f32_*_f32, the chip's specification
 PEAK_FP16_MFMA = 2.5e15
+PEAK_HBM = 8.0e12       # bytes/s, the chip's specification
 
 
 def main():
@@ -29,6 +36,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--n", type=int, default=1 << 18)
     ap.add_argument("--activation", default="ReLU")
+    ap.add_argument("--fused-ab", action="store_true", help="fp32 only: the fused forward / inference kernel against the layer-by-layer kernels")
     ap.add_argument("--out", default=None, help="also write the results to this JSON file")
     args = ap.parse_args()
     import torch
@@ -53,8 +61,55 @@ def main():
             samples.append(a.elapsed_time(b) / args.steps)
         return {"median_ms": round(statistics.median(samples), 4), "min_ms": round(min(samples), 4), "max_ms": round(max(samples), 4)}
 
-    results = []
-    for in_width, width, hidden in ((64, 64, 2), (32, 256, 4)):
+    def block(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(args.steps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / args.steps
+
+    def fused_ab():
+        out = []
+        for in_width, width, hidden, outp in ((64, 64, 2, 16), (32, 32, 3, 32)):
+            cfg = {"otype": "MLP", "activation": args.activation, "output_activation": "None", "n_neurons": width, "n_hidden_layers": hidden}
+            m = C.create_network_precision(in_width, outp, cfg, C.Precision.Fp32)
+            x = (torch.rand((n, in_width), device="cuda") * 2 - 1).requires_grad_(True)
+            p = m.initial_params(1337).requires_grad_(True)
+            x_inf, p_inf = x.detach(), p.detach()
+            saves = 2 if args.activation in ("SiLU", "Sine") else 1
+            passes = {"inference": (lambda: m.fwd(x_inf, p_inf), 4 * (in_width + outp)),
+                      "forward": (lambda: m.fwd(x, p), 4 * (in_width + outp + saves * hidden * width))}
+            for name, (fn, bytes_per_sample) in passes.items():
+                samples = {True: [], False: []}
+                try:
+                    for fused in (True, False):
+                        C.set_fp32_fused_network(fused)
+                        assert m.fp32_fused_network(n) == int(fused)
+                        for _ in range(args.warmup):
+                            fn()
+                    torch.cuda.synchronize()
+                    for _ in range(args.repeats):
+                        for fused in (True, False):
+                            C.set_fp32_fused_network(fused)
+                            samples[fused].append(block(fn))
+                finally:
+                    C.set_fp32_fused_network(True)
+                r = {"network": f"{in_width}->{width}x{hidden}->{outp}", "activation": args.activation, "pass": name, "n": n, "bytes_per_sample": bytes_per_sample}
+                for fused, key in ((True, "fused"), (False, "layer_by_layer")):
+                    med = statistics.median(samples[fused])
+                    r[key] = {"median_ms": round(med, 4), "min_ms": round(min(samples[fused]), 4), "max_ms": round(max(samples[fused]), 4),
+                              "fraction_of_hbm_roof": round(bytes_per_sample * n / (med * 1e-3) / PEAK_HBM, 4)}
+                r["speedup"] = round(r["layer_by_layer"]["median_ms"] / r["fused"]["median_ms"], 2)
+                out.append(r)
+                print(json.dumps(r), flush=True)
+            del m, x, p
+            C.free_temporary_memory()
+        return out
+
+    results = fused_ab() if args.fused_ab else []
+    for in_width, width, hidden in () if args.fused_ab else ((64, 64, 2), (32, 256, 4)):
         cfg = {"otype": "MLP", "activation": args.activation, "output_activation": "None", "n_neurons": width, "n_hidden_layers": hidden}
         macs = in_width * width + (hidden - 1) * width * width + 16 * width
         forward_flop = 2.0 * n * macs

@@ -213,6 +213,10 @@ int tcnn_module_inference_matrix(tcnn_module_t* m, tcnn_stream_t stream_, uint32
 // the modules tcnn_create_network makes (model_exec.h half_input_refusal): no fp32 copy of a matrix that a 16-bit producer wrote and the
 // network reads in 16 bits anyway.  Same bits as the fp32 entries on the widened matrix.
 int tcnn_module_supports_half_input(const tcnn_module_t* m) { return m && !m->fp32_io && half_input_refusal(m->md).empty() ? 1 : 0; }
+// what mlp_f32_forward decides for a forward / inference call of n_elements on this module, asked without making the call
+int tcnn_module_fp32_fused_network(const tcnn_module_t* m, uint32_t n_elements) {
+	return m && m->fp32_network() && g_fp32_fused_network.load() != 0 && mlp_f32_fused_supported(m->md.net.mlp, n_elements) ? 1 : 0;
+}
 
 int tcnn_module_inference_half_input(tcnn_module_t* m, tcnn_stream_t stream, uint32_t n, const void* input, void* output, void* params) {
 	TCNN_API_BEGIN

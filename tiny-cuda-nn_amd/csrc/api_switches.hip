@@ -41,6 +41,7 @@ std::atomic<int> g_fused_network_passes{1};
 std::atomic<int> g_fused_identity_input{1};
 std::atomic<int> g_finalize_in_optimizer{1};
 std::atomic<int> g_fp32_second_order{0};
+std::atomic<int> g_fp32_fused_network{1};
 
 }  // namespace tcnn_hip
 
@@ -159,6 +160,11 @@ int tcnn_get_fp32_second_order(void) { return g_fp32_second_order.load(); }
 int tcnn_set_fp32_second_order(int mode) {
 	if (mode < 0 || mode > 1) return TCNN_ERROR;
 	g_fp32_second_order.store(mode);
+	return TCNN_OK;
+}
+int tcnn_get_fp32_fused_network(void) { return g_fp32_fused_network.load(); }
+int tcnn_set_fp32_fused_network(int enable) {
+	g_fp32_fused_network.store(enable != 0 ? 1 : 0);
 	return TCNN_OK;
 }
 

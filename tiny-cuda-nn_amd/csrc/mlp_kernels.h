@@ -226,9 +226,26 @@ TCNN_HOST_DEVICE size_t mlp_f32_saved_activation_bytes(const MlpMeta& m, uint32_
 }
 // Forward.  hidden == nullptr: inference (two ping-pong matrices in stream-ordered scratch of the call).  trimmed.out given: inference into
 // the caller's trimmed matrix instead of `output` (`hidden` and `output` must be null): element (sample i, output j < dims) at
-// out[i * stride_i + j * stride_j], nothing else is written.
+// out[i * stride_i + j * stride_j], nothing else is written.  Where mlp_f32_fused_supported holds and the switch g_fp32_fused_network is on
+// (the default), all three modes run the fused kernel below instead of one launch per layer.
 void mlp_f32_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* params, const float* input, float* hidden, float* output,
                      const MlpF32Output& trimmed = {});
+// ---- the fused fp32 forward / inference kernel (mlp_f32_fused.hip): ONE launch carries a tile of 256 samples through every layer.  A wave
+// owns 32 samples; a layer's accumulator registers are the next layer's MFMA B operand as they lie (register r of a 16-neuron tile is the k-step
+// of neurons {r, 4 + r, 8 + r, 12 + r}, the A operand W[m][4 (lane >> 4) + r] comes out of LDS in one 16-byte read for all four r), so hidden
+// activations reach HBM only where the caller asked for them: never in inference, as the saved stack (same layout as above, read by
+// mlp_f32_backward / mlp_f32_backward_backward unchanged) in training.  Hidden width 16 / 32 / 64, input width a multiple of 16 up to 128,
+// padded output width a multiple of 16 up to 64, any depth, n a multiple of 256, every activation.  Same contract as mlp_f32_forward; the sum
+// over k runs in another order than the layer-by-layer kernel's, so results agree to fp32 rounding, not bit for bit (order-free inputs: bit for bit).
+constexpr uint32_t MLP_F32_FUSED_MAX_IN_WIDTH = 128;
+constexpr uint32_t MLP_F32_FUSED_MAX_OUT_WIDTH = 64;  // padded
+constexpr uint32_t MLP_F32_FUSED_TILE = 256;          // samples per workgroup tile
+TCNN_HOST_DEVICE bool mlp_f32_fused_supported(const MlpMeta& m, uint32_t n) {
+	return (m.width == 16u || m.width == 32u || m.width == 64u) && m.in_width != 0u && m.in_width % 16u == 0u && m.in_width <= MLP_F32_FUSED_MAX_IN_WIDTH &&
+	       m.padded_out != 0u && m.padded_out % 16u == 0u && m.padded_out <= MLP_F32_FUSED_MAX_OUT_WIDTH && n != 0u && n % MLP_F32_FUSED_TILE == 0u;
+}
+void mlp_f32_fused_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* params, const float* input, float* hidden, float* output,
+                           const MlpF32Output& trimmed = {});
 void mlp_f32_transpose_weights(hipStream_t stream, const MlpMeta& m, const float* params, float* params_t);
 // dL/d(pre-activation of the output layer) from dL/doutput and the output; for output activations other than None.  [n][padded_out] each.
 void mlp_f32_output_activation_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* output, const float* dL_doutput, float* dL_dpreact);

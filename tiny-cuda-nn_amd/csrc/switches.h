@@ -24,5 +24,8 @@ extern std::atomic<int> g_finalize_in_optimizer;
 // second-order pass of an fp32 grid encoding: 0 = the fp32 kernels (default), 1 = the 16-bit kernels on stand-ins of the caller's fp32 tensors
 // (tcnn_set_fp32_second_order; A/B runs, tests)
 extern std::atomic<int> g_fp32_second_order;
+// forward / inference of an fp32 network whose shape mlp_f32_fused_supported names: 1 = the fused kernel (mlp_f32_fused.hip, default), 0 = the
+// layer-by-layer kernels at every shape (tcnn_set_fp32_fused_network; A/B runs, tests, the earlier bits)
+extern std::atomic<int> g_fp32_fused_network;
 
 }  // namespace tcnn_hip

@@ -206,6 +206,9 @@ _sig("tcnn_set_grid_backward_mode", _i, _i)
 _sig("tcnn_get_grid_backward_mode", _i)
 _sig("tcnn_set_fp32_second_order", _i, _i)
 _sig("tcnn_get_fp32_second_order", _i)
+_sig("tcnn_set_fp32_fused_network", _i, _i)
+_sig("tcnn_get_fp32_fused_network", _i)
+_sig("tcnn_module_fp32_fused_network", _i, _vp, _u32)
 _sig("tcnn_set_grid_owner_mode", _i, _i)
 _sig("tcnn_get_grid_owner_mode", _i)
 _sig("tcnn_grid_owner_wide_slices", _i, C.POINTER(C.c_uint64))
@@ -318,6 +321,16 @@ def set_fp32_second_order(mode):
     16-bit kernels on stand-ins of the caller's fp32 tensors (A/B timing, tests)."""
     if _lib.tcnn_set_fp32_second_order(int(mode)) != OK:
         raise RuntimeError("set_fp32_second_order: mode must be 0 or 1")
+
+
+def get_fp32_fused_network():
+    return bool(_lib.tcnn_get_fp32_fused_network())
+
+
+def set_fp32_fused_network(enable):
+    """Forward / inference of fp32 networks with 16, 32 or 64 neurons, process-wide (both bindings call the same library): the fused kernel
+    (default) / one launch per layer at every shape (A/B timing, tests, the earlier bits)."""
+    _check(_lib.tcnn_set_fp32_fused_network(int(bool(enable))))
 
 
 def get_grid_owner_mode():
@@ -467,6 +480,10 @@ class Module:
     def supports_half_input(self):
         """True for the modules create_network makes: fwd / bwd then also take an input in the module's 16-bit type (tcnn_module_*_half_input)."""
         return self._fixed("_supports_half_input", lambda: bool(_lib.tcnn_module_supports_half_input(self._h)))
+
+    def fp32_fused_network(self, n):
+        """1 if a forward / inference call of n rows on this module would run the fused fp32 network kernel now (set_fp32_fused_network), else 0."""
+        return int(_lib.tcnn_module_fp32_fused_network(self._h, int(n)))
 
     def _takes_half(self, input):
         return input.dtype != torch.float32 and input.dtype == self._torch_param_dtype() and self.supports_half_input()
@@ -736,6 +753,7 @@ class ExtModule:
     network_layers = Module.network_layers
     bwd_into = Module.bwd_into
     inference_into = Module.inference_into
+    fp32_fused_network = Module.fp32_fused_network
 
 
 def ext_apply(module, x, params, loss_scale):
