@@ -484,6 +484,15 @@ int tcnn_get_fp32_second_order(void);
 int tcnn_set_fp32_fused_network(int enable);
 int tcnn_get_fp32_fused_network(void);
 int tcnn_module_fp32_fused_network(const tcnn_module_t* m, uint32_t n_elements);
+/* Backward of the same networks, process-wide, default 1: two fused launches (csrc/mlp_f32_fused_backward.hip) -- one kernel from dL_doutput
+ * through every hidden layer to dL_dinput, one kernel for the gradients of all weight matrices -- instead of one launch per layer and one per
+ * matrix.  0: the layer-by-layer backward pass.  tcnn_set_fp32_fused_network(0) turns this off as well (it turns off every fused fp32
+ * kernel).  Results agree to fp32 rounding (bit for bit where every sum is exact); the saved activations, backward_backward_input and every
+ * refusal are the same.  tcnn_module_fp32_fused_backward: 1 if a backward call of n_elements on this module would run the fused kernels now;
+ * 0 for 16-bit modules, bare encodings, other shapes and with either switch off. */
+int tcnn_set_fp32_fused_backward(int enable);
+int tcnn_get_fp32_fused_backward(void);
+int tcnn_module_fp32_fused_backward(const tcnn_module_t* m, uint32_t n_elements);
 /* Accumulator form of the bucket owners in mode 3, process-wide (same bits from all three): 0 = packed (default: both features of a
  * payload word in one 64-bit LDS word, half the LDS atomics and half the LDS; slices whose sums could leave int32 are redone wide),
  * 1 = 64-bit fixed point per value throughout, 2 = the packed kernel with every slice through its wide redo (tests). */

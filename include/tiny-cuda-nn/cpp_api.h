@@ -151,6 +151,8 @@ public:
 	bool supports_half_input() const { return tcnn_module_supports_half_input(m_) != 0; }
 	// Beyond the reference: would a forward / inference call of n_elements run the fused fp32 network kernel now (tcnn_set_fp32_fused_network)
 	bool fp32_fused_network(uint32_t n_elements) const { return tcnn_module_fp32_fused_network(m_, n_elements) != 0; }
+	// ... and would a backward call run the fused fp32 backward kernels now (tcnn_set_fp32_fused_backward)
+	bool fp32_fused_backward(uint32_t n_elements) const { return tcnn_module_fp32_fused_backward(m_, n_elements) != 0; }
 	void inference_half_input(hipStream_t stream, uint32_t n_elements, const void* input, void* output, void* params) {
 		check(tcnn_module_inference_half_input(m_, stream, n_elements, input, output, params));
 	}

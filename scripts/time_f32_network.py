@@ -14,7 +14,12 @@ activations (no backward).  The two settings alternate block by block (--repeats
 both); per setting the median block with the minimum and maximum.  Beside each: the bytes per sample the pass has to move (input, output,
 saved activations) and the fraction of the HBM roof the median implies.
 
-usage: python scripts/time_f32_network.py [--steps 50] [--warmup 10] [--repeats 5] [--n 262144] [--activation ReLU] [--fused-ab] [--out results.json]"""
+--fused-backward-ab: the same protocol and networks for the fused backward kernels (csrc/mlp_f32_fused_backward.hip), toggled by
+tcnn_set_fp32_fused_backward with the forward switch on in both arms: forward + backward (dL/dinput and parameter gradients), and the
+backward call alone on one saved context.
+
+usage: python scripts/time_f32_network.py [--steps 50] [--warmup 10] [--repeats 5] [--n 262144] [--activation ReLU] [--fused-ab | --fused-backward-ab]
+       [--out results.json]"""
 import argparse
 import json
 import os
@@ -37,6 +42,7 @@ def main():
     ap.add_argument("--n", type=int, default=1 << 18)
     ap.add_argument("--activation", default="ReLU")
     ap.add_argument("--fused-ab", action="store_true", help="fp32 only: the fused forward / inference kernel against the layer-by-layer kernels")
+    ap.add_argument("--fused-backward-ab", action="store_true", help="fp32 only: the fused backward kernels against the layer-by-layer backward pass")
     ap.add_argument("--out", default=None, help="also write the results to this JSON file")
     args = ap.parse_args()
     import torch
@@ -70,8 +76,9 @@ def main():
         torch.cuda.synchronize()
         return a.elapsed_time(b) / args.steps
 
-    def fused_ab():
+    def fused_ab(backward):
         out = []
+        switch, query = (C.set_fp32_fused_backward, "fp32_fused_backward") if backward else (C.set_fp32_fused_network, "fp32_fused_network")
         for in_width, width, hidden, outp in ((64, 64, 2, 16), (32, 32, 3, 32)):
             cfg = {"otype": "MLP", "activation": args.activation, "output_activation": "None", "n_neurons": width, "n_hidden_layers": hidden}
             m = C.create_network_precision(in_width, outp, cfg, C.Precision.Fp32)
@@ -81,21 +88,33 @@ def main():
             saves = 2 if args.activation in ("SiLU", "Sine") else 1
             passes = {"inference": (lambda: m.fwd(x_inf, p_inf), 4 * (in_width + outp)),
                       "forward": (lambda: m.fwd(x, p), 4 * (in_width + outp + saves * hidden * width))}
+            if backward:
+                dy = torch.rand((n, outp), device="cuda") * 2 - 1
+                ctx, y = m.fwd(x, p)
+
+                def forward_backward():
+                    c, out_ = m.fwd(x, p)
+                    m.bwd(c, x, p, out_, dy)
+
+                # backward reads dL/doutput and the stack at the derivative's values, writes dL/dinput; the gradients read the input, the
+                # post-activations and each layer's dL/d(pre-activation), which (layer by layer, or for the gradients) is also written once
+                bwd_bytes = 4 * (2 * in_width + 2 * outp + 4 * hidden * width)
+                passes = {"forward_backward": (forward_backward, passes["forward"][1] + bwd_bytes), "backward": (lambda: m.bwd(ctx, x, p, y, dy), bwd_bytes)}
             for name, (fn, bytes_per_sample) in passes.items():
                 samples = {True: [], False: []}
                 try:
                     for fused in (True, False):
-                        C.set_fp32_fused_network(fused)
-                        assert m.fp32_fused_network(n) == int(fused)
+                        switch(fused)
+                        assert getattr(m, query)(n) == int(fused)
                         for _ in range(args.warmup):
                             fn()
                     torch.cuda.synchronize()
                     for _ in range(args.repeats):
                         for fused in (True, False):
-                            C.set_fp32_fused_network(fused)
+                            switch(fused)
                             samples[fused].append(block(fn))
                 finally:
-                    C.set_fp32_fused_network(True)
+                    switch(True)
                 r = {"network": f"{in_width}->{width}x{hidden}->{outp}", "activation": args.activation, "pass": name, "n": n, "bytes_per_sample": bytes_per_sample}
                 for fused, key in ((True, "fused"), (False, "layer_by_layer")):
                     med = statistics.median(samples[fused])
@@ -108,8 +127,9 @@ def main():
             C.free_temporary_memory()
         return out
 
-    results = fused_ab() if args.fused_ab else []
-    for in_width, width, hidden in () if args.fused_ab else ((64, 64, 2), (32, 256, 4)):
+    ab = args.fused_ab or args.fused_backward_ab
+    results = fused_ab(args.fused_backward_ab) if ab else []
+    for in_width, width, hidden in () if ab else ((64, 64, 2), (32, 256, 4)):
         cfg = {"otype": "MLP", "activation": args.activation, "output_activation": "None", "n_neurons": width, "n_hidden_layers": hidden}
         macs = in_width * width + (hidden - 1) * width * width + 16 * width
         forward_flop = 2.0 * n * macs

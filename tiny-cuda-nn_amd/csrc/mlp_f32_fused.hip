@@ -27,19 +27,12 @@
 // separates the rows alone, models at 8 (scripts/lds_bank_model.py).
 // All matrices resident when they fit F32F_RESIDENT_LDS_BYTES (every network of up to 5 hidden layers at 64 neurons, 128 inputs and 64 outputs, deeper
 // ones at smaller widths); a deeper network stages one matrix at a time in a buffer of the largest, between two barriers per layer.
-#include "mlp_kernels.h"
+#include "mlp_f32_fused_device.h"
 
 #include <algorithm>
 #include <stdexcept>
 
 namespace tcnn_hip {
-
-constexpr uint32_t F32F_THREADS = 512;
-constexpr uint32_t F32F_WAVE_SAMPLES = 32;                 // two 16-column sample tiles
-constexpr uint32_t F32F_PAD = 8;                           // floats between the end of a weight row and the next row in LDS
-constexpr uint32_t F32F_RESIDENT_LDS_BYTES = 128u << 10;   // of the CU's 160 KiB
-constexpr uint32_t F32F_MAX_BLOCKS = 512;                  // two workgroups per CU where LDS and registers allow
-static_assert(F32F_THREADS / WAVE * F32F_WAVE_SAMPLES == MLP_F32_FUSED_TILE, "a workgroup's waves cover its tile");
 
 struct F32FusedArgs {
 	MlpMeta m;
@@ -53,15 +46,6 @@ struct F32FusedArgs {
 	MlpF32Output t;         // t.out given: element (i, j < dims) at out[i * stride_i + j * stride_j], nothing else written
 	uint32_t t_vec;         // 4: every (sample, multiple-of-4 column) of t is 16-byte aligned with unit column stride; else 1
 };
-
-// one weight matrix [rows][K], global -> LDS rows of K + F32F_PAD floats, 16 bytes per thread and step
-TCNN_DEVICE void f32f_copy_matrix(float* dst, const float* src, uint32_t rows, uint32_t K) {
-	const uint32_t chunks_per_row = K / 4u, chunks = rows * chunks_per_row;
-	for (uint32_t c = threadIdx.x; c < chunks; c += F32F_THREADS) {
-		const uint32_t row = c / chunks_per_row, kc = c % chunks_per_row;
-		*(f4*)(dst + row * (K + F32F_PAD) + 4u * kc) = *(const f4*)(src + (size_t)row * K + 4u * kc);
-	}
-}
 
 template <uint32_t W, bool GENERAL>
 __global__ void __launch_bounds__(F32F_THREADS) k_mlp_f32_fused(const F32FusedArgs a) {

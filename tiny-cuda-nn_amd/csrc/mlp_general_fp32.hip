@@ -65,11 +65,27 @@ void mlp_f32_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const flo
 }
 uint32_t mlp_f32_n_partials(const MlpMeta& m, uint32_t n) { return gen_n_partials<float>(m, n); }
 size_t mlp_f32_backward_workspace_bytes(const MlpMeta& m, uint32_t n) { return gen_backward_workspace_bytes<float>(m, n); }
+bool mlp_f32_backward_is_fused(const MlpMeta& m, uint32_t n) {
+#if !defined(TCNN_HOST_EMU)
+	return g_fp32_fused_network.load() != 0 && g_fp32_fused_backward.load() != 0 && mlp_f32_fused_backward_supported(m, n);
+#else
+	return false;
+#endif
+}
+uint32_t mlp_f32_backward_n_partials(const MlpMeta& m, uint32_t n) {
+#if !defined(TCNN_HOST_EMU)
+	if (mlp_f32_backward_is_fused(m, n)) return mlp_f32_fused_n_partials(m, n);
+#endif
+	return gen_n_partials<float>(m, n);
+}
 void mlp_f32_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* params_t, const float* input, const float* hidden, const float* dL_doutput,
                       float* dL_dinput, float* partials, void* workspace) {
 	g32_check_shape(m, n);
 	if (!workspace) throw std::runtime_error("mlp_f32_backward: a workspace is required (mlp_f32_backward_workspace_bytes)");
 	if (!hidden) throw std::runtime_error("mlp_f32_backward: the saved activations of the forward pass are required");
+#if !defined(TCNN_HOST_EMU)
+	if (mlp_f32_backward_is_fused(m, n)) return mlp_f32_fused_backward(stream, m, n, params_t, input, hidden, dL_doutput, dL_dinput, partials, workspace);
+#endif
 	gen_backward<float>(stream, m, n, params_t, input, hidden, dL_doutput, dL_dinput, partials, workspace);
 }
 

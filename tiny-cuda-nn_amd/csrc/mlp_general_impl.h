@@ -552,8 +552,7 @@ static void gen_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const 
 	}
 }
 
-// The fp32 slabs of all slices may take this much scratch.  512 slabs (what the fused kernels write) of a 1024 x 4 network would be 8 GB.
-constexpr size_t MLP_GENERAL_SLAB_BUDGET_BYTES = (size_t)128 << 20;
+// (the slabs of all slices stay within MLP_GENERAL_SLAB_BUDGET_BYTES, mlp_kernels.h)
 constexpr uint32_t GEN_WG_TARGET_BLOCKS = 1024;  // (tiles x slices) to aim for: four workgroups per CU
 constexpr uint32_t GEN_WG_MAX_SLICES = 32;
 

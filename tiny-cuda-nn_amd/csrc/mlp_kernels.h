@@ -88,6 +88,9 @@ constexpr uint32_t MLP_MAX_OUT_WIDTH = 128;  // padded; more than 16 outputs tra
 constexpr uint32_t MLP_GENERAL_MAX_WIDTH = 1024;
 constexpr uint32_t MLP_GENERAL_MAX_IN_WIDTH = 1024;
 constexpr uint32_t MLP_GENERAL_MAX_OUT_WIDTH = 1024;  // padded
+// The fp32 slabs of all batch slices of a layer-by-layer or fused-fp32 backward pass may take this much scratch.  512 slabs (what the fused
+// 16-bit kernels write) of a 1024 x 4 network would be 8 GB.
+constexpr size_t MLP_GENERAL_SLAB_BUDGET_BYTES = (size_t)128 << 20;
 // the widths the fused kernels are instantiated for
 TCNN_HOST_DEVICE bool mlp_fused_width(uint32_t width) { return width == 16u || width == 32u || width == 64u || width == 128u; }
 // THE place that decides the path: true -> mlp_general.hip, and every fused kernel's *_supported predicate is false
@@ -246,13 +249,29 @@ TCNN_HOST_DEVICE bool mlp_f32_fused_supported(const MlpMeta& m, uint32_t n) {
 }
 void mlp_f32_fused_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* params, const float* input, float* hidden, float* output,
                            const MlpF32Output& trimmed = {});
+// ---- the fused fp32 backward pass (mlp_f32_fused_backward.hip), two launches: a chain kernel on the same register hand-over (dL_doutput ->
+// D_j of every hidden layer -> dL_dinput; the D_j reach the workspace only where weight gradients were asked for), and ONE weight-gradient
+// kernel for all matrices over mlp_f32_fused_n_partials batch slices.  Same contract as mlp_f32_backward, which routes here where
+// mlp_f32_fused_backward_supported holds and both switches (g_fp32_fused_network, g_fp32_fused_backward) are on; the slabs are then
+// [mlp_f32_fused_n_partials][n_params] -- mlp_f32_backward_n_partials names the count either way.  Sums over k and over the batch run in
+// another order than the layer-by-layer kernels': results agree to fp32 rounding (order-free inputs: bit for bit).
+TCNN_HOST_DEVICE bool mlp_f32_fused_backward_supported(const MlpMeta& m, uint32_t n) { return mlp_f32_fused_supported(m, n); }
+// A power of two, at most n / 256, within MLP_GENERAL_SLAB_BUDGET_BYTES, aiming at four workgroups per CU over all matrices: a function of
+// the network and the batch size alone.
+uint32_t mlp_f32_fused_n_partials(const MlpMeta& m, uint32_t n);
+void mlp_f32_fused_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* params_t, const float* input, const float* hidden, const float* dL_doutput,
+                            float* dL_dinput, float* partials, void* workspace);
+// would mlp_f32_backward(m, n) run the fused kernels now / how many slabs does it write now: what its caller sizes and finalizes `partials`
+// with.  (The second-order pass keeps mlp_f32_n_partials: it runs the layer-by-layer weight-gradient kernel at every shape.)
+bool mlp_f32_backward_is_fused(const MlpMeta& m, uint32_t n);
+uint32_t mlp_f32_backward_n_partials(const MlpMeta& m, uint32_t n);
 void mlp_f32_transpose_weights(hipStream_t stream, const MlpMeta& m, const float* params, float* params_t);
 // dL/d(pre-activation of the output layer) from dL/doutput and the output; for output activations other than None.  [n][padded_out] each.
 void mlp_f32_output_activation_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* output, const float* dL_doutput, float* dL_dpreact);
 // Number of batch slices == fp32 slabs of the weight-gradient products: a function of the network and the batch size alone.
 uint32_t mlp_f32_n_partials(const MlpMeta& m, uint32_t n);
 size_t mlp_f32_backward_workspace_bytes(const MlpMeta& m, uint32_t n);  // dL/d(pre-activation) of every hidden layer
-// dL_doutput: w.r.t. the output layer's pre-activation.  dL_dinput and partials ([mlp_f32_n_partials][n_params]) may be null.
+// dL_doutput: w.r.t. the output layer's pre-activation.  dL_dinput and partials ([mlp_f32_backward_n_partials][n_params]) may be null.
 void mlp_f32_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* params_t, const float* input, const float* hidden, const float* dL_doutput,
                       float* dL_dinput, float* partials, void* workspace);
 // grads[i] = (accumulate ? grads[i] : 0) + (partials[0][i] + partials[1][i] + ...), slabs in ascending order

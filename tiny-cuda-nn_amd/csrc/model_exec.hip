@@ -390,7 +390,7 @@ void model_backward_f32(hipStream_t stream, const Model& md, const IoLayout& lay
 	const bool need_denc = (want_grads && e.n_params > 0) || dL_dinput;
 	Scratch params_t(stream, md.n_mlp_params() * sizeof(float));
 	mlp_f32_transpose_weights(stream, mlp, params, params_t.as<float>());
-	const uint32_t n_partials = mlp_f32_n_partials(mlp, n);
+	const uint32_t n_partials = mlp_f32_backward_n_partials(mlp, n);  // (of the kernels mlp_f32_backward runs now: fused or layer by layer)
 	Scratch partials, denc, dpre;
 	if (want_grads) partials = Scratch(stream, (size_t)n_partials * md.n_mlp_params() * sizeof(float));
 	if (need_denc) denc = Scratch(stream, (size_t)e.padded_output_width * n * sizeof(float));

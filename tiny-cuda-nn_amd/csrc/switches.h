@@ -27,5 +27,9 @@ extern std::atomic<int> g_fp32_second_order;
 // forward / inference of an fp32 network whose shape mlp_f32_fused_supported names: 1 = the fused kernel (mlp_f32_fused.hip, default), 0 = the
 // layer-by-layer kernels at every shape (tcnn_set_fp32_fused_network; A/B runs, tests, the earlier bits)
 extern std::atomic<int> g_fp32_fused_network;
+// backward of an fp32 network whose shape mlp_f32_fused_backward_supported names: 1 = the fused chain and weight-gradient kernels
+// (mlp_f32_fused_backward.hip, default), 0 = the layer-by-layer kernels (tcnn_set_fp32_fused_backward).  Read together with
+// g_fp32_fused_network: that switch at 0 turns off every fused fp32 kernel, this one the backward pass alone.
+extern std::atomic<int> g_fp32_fused_backward;
 
 }  // namespace tcnn_hip

@@ -209,6 +209,9 @@ _sig("tcnn_get_fp32_second_order", _i)
 _sig("tcnn_set_fp32_fused_network", _i, _i)
 _sig("tcnn_get_fp32_fused_network", _i)
 _sig("tcnn_module_fp32_fused_network", _i, _vp, _u32)
+_sig("tcnn_set_fp32_fused_backward", _i, _i)
+_sig("tcnn_get_fp32_fused_backward", _i)
+_sig("tcnn_module_fp32_fused_backward", _i, _vp, _u32)
 _sig("tcnn_set_grid_owner_mode", _i, _i)
 _sig("tcnn_get_grid_owner_mode", _i)
 _sig("tcnn_grid_owner_wide_slices", _i, C.POINTER(C.c_uint64))
@@ -331,6 +334,16 @@ def set_fp32_fused_network(enable):
     """Forward / inference of fp32 networks with 16, 32 or 64 neurons, process-wide (both bindings call the same library): the fused kernel
     (default) / one launch per layer at every shape (A/B timing, tests, the earlier bits)."""
     _check(_lib.tcnn_set_fp32_fused_network(int(bool(enable))))
+
+
+def get_fp32_fused_backward():
+    return bool(_lib.tcnn_get_fp32_fused_backward())
+
+
+def set_fp32_fused_backward(enable):
+    """Backward of the same fp32 networks, process-wide: the fused chain and weight-gradient kernels (default) / one launch per layer and
+    matrix.  set_fp32_fused_network(False) turns the fused backward off as well."""
+    _check(_lib.tcnn_set_fp32_fused_backward(int(bool(enable))))
 
 
 def get_grid_owner_mode():
@@ -484,6 +497,10 @@ class Module:
     def fp32_fused_network(self, n):
         """1 if a forward / inference call of n rows on this module would run the fused fp32 network kernel now (set_fp32_fused_network), else 0."""
         return int(_lib.tcnn_module_fp32_fused_network(self._h, int(n)))
+
+    def fp32_fused_backward(self, n):
+        """1 if a backward call of n rows on this module would run the fused fp32 backward kernels now (set_fp32_fused_backward), else 0."""
+        return int(_lib.tcnn_module_fp32_fused_backward(self._h, int(n)))
 
     def _takes_half(self, input):
         return input.dtype != torch.float32 and input.dtype == self._torch_param_dtype() and self.supports_half_input()
@@ -754,6 +771,7 @@ class ExtModule:
     bwd_into = Module.bwd_into
     inference_into = Module.inference_into
     fp32_fused_network = Module.fp32_fused_network
+    fp32_fused_backward = Module.fp32_fused_backward
 
 
 def ext_apply(module, x, params, loss_scale):
