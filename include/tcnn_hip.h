@@ -493,6 +493,16 @@ int tcnn_module_fp32_fused_network(const tcnn_module_t* m, uint32_t n_elements);
 int tcnn_set_fp32_fused_backward(int enable);
 int tcnn_get_fp32_fused_backward(void);
 int tcnn_module_fp32_fused_backward(const tcnn_module_t* m, uint32_t n_elements);
+/* Second-order pass (tcnn_module_backward_backward_input) of the same networks, process-wide, default 1: at most three fused launches
+ * (csrc/mlp_f32_fused_second_order.hip) -- the tangent chain with the output activation's terms, the reverse chain that carries the
+ * first-order and the curvature recurrence together down to dL_dinput, one dual weight-gradient kernel for all matrices -- instead of one
+ * launch per layer, chain and matrix.  0: the layer-by-layer pass.  tcnn_set_fp32_fused_network(0) and tcnn_set_fp32_fused_backward(0) turn
+ * this off as well.  Results agree to fp32 rounding (bit for bit where every sum is exact); the contract, the nullable results and every
+ * refusal are the same.  tcnn_module_fp32_fused_second_order: 1 if a backward_backward_input call of n_elements on this module would run the
+ * fused kernels now; 0 for 16-bit modules, bare encodings, other shapes and with any of the three switches off. */
+int tcnn_set_fp32_fused_second_order(int enable);
+int tcnn_get_fp32_fused_second_order(void);
+int tcnn_module_fp32_fused_second_order(const tcnn_module_t* m, uint32_t n_elements);
 /* Accumulator form of the bucket owners in mode 3, process-wide (same bits from all three): 0 = packed (default: both features of a
  * payload word in one 64-bit LDS word, half the LDS atomics and half the LDS; slices whose sums could leave int32 are redone wide),
  * 1 = 64-bit fixed point per value throughout, 2 = the packed kernel with every slice through its wide redo (tests). */

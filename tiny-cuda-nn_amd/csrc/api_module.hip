@@ -221,6 +221,10 @@ int tcnn_module_fp32_fused_network(const tcnn_module_t* m, uint32_t n_elements) 
 int tcnn_module_fp32_fused_backward(const tcnn_module_t* m, uint32_t n_elements) {
 	return m && m->fp32_network() && mlp_f32_backward_is_fused(m->md.net.mlp, n_elements) ? 1 : 0;
 }
+// what mlp_f32_backward_backward decides for a backward_backward_input call of n_elements on this module
+int tcnn_module_fp32_fused_second_order(const tcnn_module_t* m, uint32_t n_elements) {
+	return m && m->fp32_network() && mlp_f32_backward_backward_is_fused(m->md.net.mlp, n_elements) ? 1 : 0;
+}
 
 int tcnn_module_inference_half_input(tcnn_module_t* m, tcnn_stream_t stream, uint32_t n, const void* input, void* output, void* params) {
 	TCNN_API_BEGIN

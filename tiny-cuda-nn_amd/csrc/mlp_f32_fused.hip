@@ -197,14 +197,6 @@ __global__ void __launch_bounds__(F32F_THREADS) k_mlp_f32_fused(const F32FusedAr
 	}
 }
 
-// floats of LDS with every matrix resident / of the staging buffer (the largest matrix)
-static uint32_t f32f_resident_floats(const MlpMeta& m) {
-	return m.width * (m.in_width + F32F_PAD) + (m.n_hidden_matmuls * m.width + m.padded_out) * (m.width + F32F_PAD);
-}
-static uint32_t f32f_staged_floats(const MlpMeta& m) {
-	return std::max(m.width * (m.in_width + F32F_PAD), std::max(m.width, m.padded_out) * (m.width + F32F_PAD));
-}
-
 template <uint32_t W>
 static void f32f_launch(hipStream_t stream, const F32FusedArgs& a) {
 	const uint32_t floats = a.resident ? f32f_resident_floats(a.m) : f32f_staged_floats(a.m);

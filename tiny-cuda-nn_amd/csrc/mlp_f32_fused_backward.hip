@@ -31,6 +31,7 @@
 //    Slice s covers the sample tiles [s T / S, (s + 1) T / S) -- any T >= S -- in ascending order and writes every element of its slab
 //    ([slab][n_params], parameter order) exactly once; k_mlp_f32_finalize sums the slabs in ascending order.  S = mlp_f32_fused_n_partials(m, n)
 //    depends on the network and n alone, so results depend neither on the launch geometry nor on earlier calls.
+//    (The kernel itself stands in mlp_f32_fused_device.h: the second-order pass instantiates it with two operand pairs.)
 #include "mlp_f32_fused_device.h"
 
 #include <algorithm>
@@ -190,14 +191,6 @@ __global__ void __launch_bounds__(F32F_THREADS) k_mlp_f32_backward_chain(const F
 	}
 }
 
-// floats of LDS with every matrix resident / of the staging buffer (the largest matrix); the input matrix only where dL_dinput is computed
-static uint32_t f32b_resident_floats(const MlpMeta& m, bool want_dx) {
-	return m.width * (m.padded_out + F32F_PAD) + (m.n_hidden_matmuls * m.width + (want_dx ? m.in_width : 0u)) * (m.width + F32F_PAD);
-}
-static uint32_t f32b_staged_floats(const MlpMeta& m, bool want_dx) {
-	return std::max(m.width * (m.padded_out + F32F_PAD), std::max(m.width, want_dx ? m.in_width : 0u) * (m.width + F32F_PAD));
-}
-
 template <uint32_t W>
 static void f32b_launch_chain(hipStream_t stream, const F32ChainArgs& a) {
 	const bool want_dx = a.dL_dinput != nullptr;
@@ -213,132 +206,23 @@ static void f32b_launch_chain(hipStream_t stream, const F32ChainArgs& a) {
 	}
 }
 
-// ---- weight gradients -----------------------------------------------------------------------------------------------------------------
-constexpr uint32_t F32G_THREADS = 512;
-constexpr uint32_t F32G_BS = 32;                  // samples per LDS stage
-constexpr uint32_t F32G_LDF = F32G_BS + 4;        // row stride of the feature-major stage [feature][sample]
-constexpr uint32_t F32G_TARGET_BLOCKS = 1024;     // (matrices x slices) to aim for: four workgroups per CU
-static_assert(MLP_F32_FUSED_TILE % F32G_BS == 0, "a sample tile is a whole number of stages");
-
-// row stride of a sample-major stage [sample][width]: the four rows of a "samples in k" read 16 banks apart, and room for the second tile of
-// a wave's 2 x 2 block where the matrix has an odd number of tiles
-TCNN_HOST_DEVICE uint32_t f32g_ld(uint32_t width) { return next_multiple(width, 32u) + 16u; }
-
-struct F32WgradArgs {
-	MlpMeta m;
-	uint32_t n, n_slices;
-	uint32_t stage_floats;    // of one LDS stage: the largest matrix's
-	const float* dact;        // [n_hidden][n][W] D_j
-	const float* dL_doutput;  // [n][padded_out]
-	const float* hidden;      // [n_hidden][n][W] post-activations
-	const float* input;       // feature-major [in_width][n]
-	float* partials;          // [n_slices][n_params]
-};
-
-__global__ void __launch_bounds__(F32G_THREADS) k_mlp_f32_wgrad_all(const F32WgradArgs p) {
-	constexpr uint32_t BS = F32G_BS, LDF = F32G_LDF, CS = BS / 4u;
-	TCNN_DYN_LDS(lds_raw);
-	float* lds = (float*)lds_raw;
-
-	const uint32_t tid = threadIdx.x, w = tid >> 6, lane = tid & 63u, lr = lane & 15u, g = lane >> 4;
-	const uint32_t W = p.m.width, IN = p.m.in_width, HM = p.m.n_hidden_matmuls, OUTP = p.m.padded_out;
-	const uint32_t n_matrices = HM + 2u, mi = blockIdx.x % n_matrices, slice = blockIdx.x / n_matrices;
-	const size_t n = p.n, layer_elems = n * W;
-	// this item's matrix [WO][WI] (uniform)
-	const bool fm = mi == 0u, out = mi == HM + 1u;
-	const uint32_t WO = out ? OUTP : W, WI = fm ? IN : W;
-	const float* d = out ? p.dL_doutput : p.dact + mi * layer_elems;   // sample-major [n][WO]
-	const float* av_src = fm ? p.input : p.hidden + (mi - 1u) * layer_elems;  // feature-major [IN][n], or sample-major [n][W]
-	const size_t offset = fm ? 0u : (size_t)W * IN + (size_t)(mi - 1u) * W * W;
-	const uint32_t ldd = f32g_ld(WO), lda = f32g_ld(WI);
-	const uint32_t ckd = WO / 4u, d_chunks = BS * ckd;                    // 16-byte chunks of a stage: <= 512
-	const uint32_t cka = WI / 4u, a_chunks = fm ? WI * CS : BS * cka;      // <= 1024 (feature-major), <= 512
-
-	// this wave's 2 x 2 block of 16 x 16 tiles
-	const uint32_t nbi = div_round_up(WI, 32u), wo = w / nbi, wi = w % nbi;
-	const bool active = 32u * wo < WO;  // (uniform per wave)
-	// the tiles of slice s: [s T / S, (s + 1) T / S), in stages of BS samples
-	const uint32_t n_tiles = p.n / MLP_F32_FUSED_TILE, per_tile = MLP_F32_FUSED_TILE / BS;
-	const uint32_t t_begin = (uint32_t)((uint64_t)slice * n_tiles / p.n_slices) * per_tile, t_end = (uint32_t)((uint64_t)(slice + 1u) * n_tiles / p.n_slices) * per_tile;
-
-	f4 dreg, areg[2];
-	auto load = [&](uint32_t t) {
-		const size_t s = (size_t)t * BS;
-		if (tid < d_chunks) dreg = *(const f4*)(d + (s + tid / ckd) * WO + 4u * (tid % ckd));
-#pragma unroll
-		for (uint32_t q = 0; q < 2; ++q) {
-			const uint32_t c = tid + q * F32G_THREADS;
-			if (c < a_chunks) {
-				areg[q] = fm ? *(const f4*)(av_src + (size_t)(c / CS) * n + s + 4u * (c % CS)) : *(const f4*)(av_src + (s + c / cka) * W + 4u * (c % cka));
-			}
-		}
-	};
-	auto store = [&](float* stage) {
-		float* dT = stage;
-		float* aT = stage + BS * ldd;
-		if (tid < d_chunks) *(f4*)(dT + (tid / ckd) * ldd + 4u * (tid % ckd)) = dreg;
-#pragma unroll
-		for (uint32_t q = 0; q < 2; ++q) {
-			const uint32_t c = tid + q * F32G_THREADS;
-			if (c < a_chunks) *(f4*)(aT + (fm ? (c / CS) * LDF + 4u * (c % CS) : (c / cka) * lda + 4u * (c % cka))) = areg[q];
-		}
-	};
-	// "samples in k": step q of a stage is samples 4 q + g.  d: row 4 q + g, column = this lane's row of the tile; a: the same (sample-major)
-	// or row = this lane's feature, column 4 q + g (feature-major).  Tiles past the matrix read staged or unwritten LDS inside the stage and
-	// are not stored.
-	const uint32_t d_at = g * ldd + 32u * wo + lr, d_step = 4u * ldd;
-	const uint32_t a_at = fm ? (32u * wi + lr) * LDF + g : g * lda + 32u * wi + lr, a_step = fm ? 4u : 4u * lda, a_tile = fm ? 16u * LDF : 16u;
-
-	f4 acc[2][2] = {{zero4(), zero4()}, {zero4(), zero4()}};
-	load(t_begin);
-	store(lds);
-	__syncthreads();
-	for (uint32_t t = t_begin; t < t_end; ++t) {
-		const float* dT = lds + ((t - t_begin) & 1u) * p.stage_floats;
-		const float* aT = dT + BS * ldd;
-		const bool more = t + 1u < t_end;
-		if (more) load(t + 1u);
-		if (active) {
-#pragma unroll
-			for (uint32_t q = 0; q < BS / 4u; ++q) {
-				float av[2], bv[2];
-#pragma unroll
-				for (uint32_t b = 0; b < 2; ++b) {
-					av[b] = dT[d_at + q * d_step + 16u * b];
-					bv[b] = aT[a_at + q * a_step + b * a_tile];
-				}
-#pragma unroll
-				for (uint32_t oi = 0; oi < 2; ++oi)
-#pragma unroll
-					for (uint32_t ii = 0; ii < 2; ++ii) acc[oi][ii] = mfma_16x16x4_f32(av[oi], bv[ii], acc[oi][ii]);
-			}
-		}
-		if (more) store(lds + ((t + 1u - t_begin) & 1u) * p.stage_floats);
-		__syncthreads();
+void mlp_f32_fused_backward_chain(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* params_t, const float* at, const float* dL_doutput, float* dL_dinput,
+                                  float* dact) {
+	F32ChainArgs a;
+	a.m = m;
+	a.n = n;
+	a.n_tiles = n / MLP_F32_FUSED_TILE;
+	a.resident = f32b_resident_floats(m, dL_dinput != nullptr) * sizeof(float) <= F32F_RESIDENT_LDS_BYTES ? 1u : 0u;
+	a.params_t = params_t;
+	a.at = at;
+	a.dL_doutput = dL_doutput;
+	a.dL_dinput = dL_dinput;
+	a.dact = dact;
+	switch (m.width) {
+		case 16: f32b_launch_chain<16>(stream, a); break;
+		case 32: f32b_launch_chain<32>(stream, a); break;
+		default: f32b_launch_chain<64>(stream, a); break;
 	}
-
-	// this slice's slab, parameter order; accumulator element r <-> (out = 4 g + r, in = lr) of its 16 x 16 tile
-	float* P = p.partials + (size_t)slice * p.m.n_params() + offset;
-#pragma unroll
-	for (uint32_t oi = 0; oi < 2; ++oi) {
-#pragma unroll
-		for (uint32_t ii = 0; ii < 2; ++ii) {
-			const uint32_t ob = 32u * wo + 16u * oi, ib = 32u * wi + 16u * ii;
-			f4 v = acc[oi][ii];
-			mfma_settle(v);  // read on the far side of the branch below
-			if (active && ob < WO && ib < WI) {
-#pragma unroll
-				for (uint32_t r = 0; r < 4; ++r) P[(size_t)(ob + 4u * g + r) * WI + ib + lr] = v[r];
-			}
-		}
-	}
-}
-
-// one LDS stage of the largest matrix: d [BS][ld] and a [BS][ld], or a feature-major [features in whole 2 x 2 blocks][LDF]
-static uint32_t f32g_stage_floats(const MlpMeta& m) {
-	const uint32_t input = F32G_BS * f32g_ld(m.width) + std::max(F32G_BS * f32g_ld(m.in_width), next_multiple(m.in_width, 32u) * F32G_LDF);
-	const uint32_t others = F32G_BS * f32g_ld(std::max(m.width, m.padded_out)) + F32G_BS * f32g_ld(m.width);
-	return std::max(input, others);
 }
 
 uint32_t mlp_f32_fused_n_partials(const MlpMeta& m, uint32_t n) {
@@ -358,21 +242,8 @@ void mlp_f32_fused_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, co
 	if (partials && (!workspace || !input)) throw std::runtime_error("mlp_f32_fused_backward: weight gradients need the workspace and the network input");
 	if (!dL_dinput && !partials) return;
 	const uint32_t L = m.n_hidden_matmuls + 1u;
-	F32ChainArgs a;
-	a.m = m;
-	a.n = n;
-	a.n_tiles = n / MLP_F32_FUSED_TILE;
-	a.resident = f32b_resident_floats(m, dL_dinput != nullptr) * sizeof(float) <= F32F_RESIDENT_LDS_BYTES ? 1u : 0u;
-	a.params_t = params_t;
-	a.at = act_needs_preactivation(m.activation) ? hidden + (size_t)L * n * m.width : hidden;
-	a.dL_doutput = dL_doutput;
-	a.dL_dinput = dL_dinput;
-	a.dact = partials ? (float*)workspace : nullptr;
-	switch (m.width) {
-		case 16: f32b_launch_chain<16>(stream, a); break;
-		case 32: f32b_launch_chain<32>(stream, a); break;
-		default: f32b_launch_chain<64>(stream, a); break;
-	}
+	mlp_f32_fused_backward_chain(stream, m, n, params_t, act_needs_preactivation(m.activation) ? hidden + (size_t)L * n * m.width : hidden, dL_doutput, dL_dinput,
+	                             partials ? (float*)workspace : nullptr);
 	if (!partials) return;
 
 	F32WgradArgs p;
@@ -386,7 +257,7 @@ void mlp_f32_fused_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, co
 	p.input = input;
 	p.partials = partials;
 	const uint32_t lds_bytes = 2u * p.stage_floats * (uint32_t)sizeof(float);  // <= 56 KiB
-	TCNN_LAUNCH(k_mlp_f32_wgrad_all, dim3((m.n_hidden_matmuls + 2u) * p.n_slices), dim3(F32G_THREADS), lds_bytes, stream, p);
+	TCNN_LAUNCH((k_mlp_f32_wgrad_all<F32WgradArgs>), dim3((m.n_hidden_matmuls + 2u) * p.n_slices), dim3(F32G_THREADS), lds_bytes, stream, p);
 }
 
 }  // namespace tcnn_hip

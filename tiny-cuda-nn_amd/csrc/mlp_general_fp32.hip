@@ -78,6 +78,19 @@ uint32_t mlp_f32_backward_n_partials(const MlpMeta& m, uint32_t n) {
 #endif
 	return gen_n_partials<float>(m, n);
 }
+bool mlp_f32_backward_backward_is_fused(const MlpMeta& m, uint32_t n) {
+#if !defined(TCNN_HOST_EMU)
+	return g_fp32_fused_network.load() != 0 && g_fp32_fused_backward.load() != 0 && g_fp32_fused_second_order.load() != 0 && mlp_f32_fused_supported(m, n);
+#else
+	return false;
+#endif
+}
+uint32_t mlp_f32_backward_backward_n_partials(const MlpMeta& m, uint32_t n) {
+#if !defined(TCNN_HOST_EMU)
+	if (mlp_f32_backward_backward_is_fused(m, n)) return mlp_f32_fused_n_partials(m, n);
+#endif
+	return gen_n_partials<float>(m, n);
+}
 void mlp_f32_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* params_t, const float* input, const float* hidden, const float* dL_doutput,
                       float* dL_dinput, float* partials, void* workspace) {
 	g32_check_shape(m, n);
@@ -166,6 +179,11 @@ void mlp_f32_backward_backward(hipStream_t stream, const MlpMeta& m, uint32_t n,
 	g32_check_shape(m, n);
 	if (!workspace) throw std::runtime_error("mlp_f32_backward_backward: a workspace is required (mlp_f32_backward_backward_workspace_bytes)");
 	if (!hidden || !input || !v || !params) throw std::runtime_error("mlp_f32_backward_backward: the saved activations, the encoded input, v and the parameters are required");
+#if !defined(TCNN_HOST_EMU)
+	if (mlp_f32_backward_backward_is_fused(m, n)) {
+		return mlp_f32_fused_backward_backward(stream, m, n, params, params_t, input, hidden, v, dL_doutput, dL_ddLdoutput, dL_dinput, partials, workspace);
+	}
+#endif
 	const uint32_t W = m.width, IN = m.in_width, HM = m.n_hidden_matmuls, OUTP = m.padded_out, L = HM + 1u;
 	const uint32_t act = m.activation, out_act = m.output_activation, none = (uint32_t)Activation::None;
 	const size_t LW = (size_t)n * W, LO = (size_t)n * OUTP;

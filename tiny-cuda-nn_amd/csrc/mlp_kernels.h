@@ -262,9 +262,18 @@ uint32_t mlp_f32_fused_n_partials(const MlpMeta& m, uint32_t n);
 void mlp_f32_fused_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* params_t, const float* input, const float* hidden, const float* dL_doutput,
                             float* dL_dinput, float* partials, void* workspace);
 // would mlp_f32_backward(m, n) run the fused kernels now / how many slabs does it write now: what its caller sizes and finalizes `partials`
-// with.  (The second-order pass keeps mlp_f32_n_partials: it runs the layer-by-layer weight-gradient kernel at every shape.)
+// with.  The same two for mlp_f32_backward_backward(m, n): fused where the shape is supported and g_fp32_fused_network,
+// g_fp32_fused_backward and g_fp32_fused_second_order are all on (then mlp_f32_fused_n_partials slabs), else mlp_f32_n_partials slabs of the
+// layer-by-layer weight-gradient kernel.
 bool mlp_f32_backward_is_fused(const MlpMeta& m, uint32_t n);
 uint32_t mlp_f32_backward_n_partials(const MlpMeta& m, uint32_t n);
+bool mlp_f32_backward_backward_is_fused(const MlpMeta& m, uint32_t n);
+uint32_t mlp_f32_backward_backward_n_partials(const MlpMeta& m, uint32_t n);
+// ---- the fused second-order pass (mlp_f32_fused_second_order.hip), at most three launches: the tangent chain (forward weights; also y and
+// the output activation's terms), the reverse chain carrying d_j and c_j together on one read of each transposed weight row, and the dual
+// weight-gradient kernel over mlp_f32_fused_n_partials slices.  Same contract and workspace bound as mlp_f32_backward_backward, which routes here.
+void mlp_f32_fused_backward_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* params, const float* params_t, const float* input, const float* hidden,
+                                     const float* v, const float* dL_doutput, float* dL_ddLdoutput, float* dL_dinput, float* partials, void* workspace);
 void mlp_f32_transpose_weights(hipStream_t stream, const MlpMeta& m, const float* params, float* params_t);
 // dL/d(pre-activation of the output layer) from dL/doutput and the output; for output activations other than None.  [n][padded_out] each.
 void mlp_f32_output_activation_backward(hipStream_t stream, const MlpMeta& m, uint32_t n, const float* output, const float* dL_doutput, float* dL_dpreact);
@@ -280,7 +289,7 @@ void mlp_f32_finalize_gradients(hipStream_t stream, const MlpMeta& m, uint32_t n
 // w.r.t. the network's OUTPUT here: the output activation's derivative is applied inside) with respect to dL_doutput, the network input and the
 // weights.  v: feature-major [in_width][n] like `input`, zero in the rows the encoding padded.  Each of the three results may be null, and
 // only the launches a requested one needs are made: dL_ddLdoutput [n][padded_out]; dL_dinput feature-major [in_width][n]; partials
-// ([mlp_f32_n_partials][n_params], to be summed by mlp_f32_finalize_gradients).  dL_doutput and params_t are needed for the last two only.
+// ([mlp_f32_backward_backward_n_partials][n_params], to be summed by mlp_f32_finalize_gradients).  dL_doutput and params_t are needed for the last two only.
 // Where neither activation has a second derivative (None / ReLU / LeakyReLU) dL_dinput is zeros.
 bool mlp_f32_second_order_has_curvature(const MlpMeta& m);
 size_t mlp_f32_backward_backward_workspace_bytes(const MlpMeta& m, uint32_t n);

@@ -438,7 +438,7 @@ void model_backward_backward_f32(hipStream_t stream, const Model& md, const IoLa
 		params_t = Scratch(stream, md.n_mlp_params() * sizeof(float));
 		mlp_f32_transpose_weights(stream, mlp, params, params_t.as<float>());
 	}
-	const uint32_t n_partials = mlp_f32_n_partials(mlp, n);
+	const uint32_t n_partials = mlp_f32_backward_backward_n_partials(mlp, n);
 	if (dL_dparams) partials = Scratch(stream, (size_t)n_partials * md.n_mlp_params() * sizeof(float));
 	if (dL_dinput) denc = Scratch(stream, (size_t)IN * n * sizeof(float));
 	Scratch workspace(stream, mlp_f32_backward_backward_workspace_bytes(mlp, n));

@@ -31,5 +31,9 @@ extern std::atomic<int> g_fp32_fused_network;
 // (mlp_f32_fused_backward.hip, default), 0 = the layer-by-layer kernels (tcnn_set_fp32_fused_backward).  Read together with
 // g_fp32_fused_network: that switch at 0 turns off every fused fp32 kernel, this one the backward pass alone.
 extern std::atomic<int> g_fp32_fused_backward;
+// second-order pass of the same networks: 1 = the fused tangent chain, reverse chain and dual weight-gradient kernels
+// (mlp_f32_fused_second_order.hip, default), 0 = the layer-by-layer launches (tcnn_set_fp32_fused_second_order).  Read together with the
+// two switches above: either of them at 0 turns the fused second-order pass off as well.
+extern std::atomic<int> g_fp32_fused_second_order;
 
 }  // namespace tcnn_hip

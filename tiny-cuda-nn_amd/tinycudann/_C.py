@@ -212,6 +212,9 @@ _sig("tcnn_module_fp32_fused_network", _i, _vp, _u32)
 _sig("tcnn_set_fp32_fused_backward", _i, _i)
 _sig("tcnn_get_fp32_fused_backward", _i)
 _sig("tcnn_module_fp32_fused_backward", _i, _vp, _u32)
+_sig("tcnn_set_fp32_fused_second_order", _i, _i)
+_sig("tcnn_get_fp32_fused_second_order", _i)
+_sig("tcnn_module_fp32_fused_second_order", _i, _vp, _u32)
 _sig("tcnn_set_grid_owner_mode", _i, _i)
 _sig("tcnn_get_grid_owner_mode", _i)
 _sig("tcnn_grid_owner_wide_slices", _i, C.POINTER(C.c_uint64))
@@ -344,6 +347,17 @@ def set_fp32_fused_backward(enable):
     """Backward of the same fp32 networks, process-wide: the fused chain and weight-gradient kernels (default) / one launch per layer and
     matrix.  set_fp32_fused_network(False) turns the fused backward off as well."""
     _check(_lib.tcnn_set_fp32_fused_backward(int(bool(enable))))
+
+
+def get_fp32_fused_second_order():
+    return bool(_lib.tcnn_get_fp32_fused_second_order())
+
+
+def set_fp32_fused_second_order(enable):
+    """Second-order pass (bwd_bwd_input) of the same fp32 networks, process-wide: the fused tangent chain, reverse chain and dual
+    weight-gradient kernels (default) / one launch per layer, chain and matrix.  set_fp32_fused_network(False) and
+    set_fp32_fused_backward(False) turn the fused second-order pass off as well."""
+    _check(_lib.tcnn_set_fp32_fused_second_order(int(bool(enable))))
 
 
 def get_grid_owner_mode():
@@ -501,6 +515,10 @@ class Module:
     def fp32_fused_backward(self, n):
         """1 if a backward call of n rows on this module would run the fused fp32 backward kernels now (set_fp32_fused_backward), else 0."""
         return int(_lib.tcnn_module_fp32_fused_backward(self._h, int(n)))
+
+    def fp32_fused_second_order(self, n):
+        """1 if a bwd_bwd_input call of n rows on this module would run the fused fp32 second-order kernels now (set_fp32_fused_second_order), else 0."""
+        return int(_lib.tcnn_module_fp32_fused_second_order(self._h, int(n)))
 
     def _takes_half(self, input):
         return input.dtype != torch.float32 and input.dtype == self._torch_param_dtype() and self.supports_half_input()
@@ -772,6 +790,7 @@ class ExtModule:
     inference_into = Module.inference_into
     fp32_fused_network = Module.fp32_fused_network
     fp32_fused_backward = Module.fp32_fused_backward
+    fp32_fused_second_order = Module.fp32_fused_second_order
 
 
 def ext_apply(module, x, params, loss_scale):
