@@ -32,6 +32,7 @@ _VARIANTS = {(keep, bf16): (os.path.join(_HERE, "libtcnn_emu%s%s.so" % ("_keep" 
 # exports its state or can bind to another's, so all can live in one process (ctypes loads them RTLD_LOCAL).
 _COMPILE = [_CLANG, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wno-pass-failed",
             "-DTCNN_MLP_WAVE_BLOCKS=3",  # few workgroups: the persistent strip loop runs uneven shares
+            "-DTCNN_F32F_MAX_BLOCKS=2",  # the fused fp32 chains likewise: of three sample tiles one workgroup takes tiles 0 and 2, the other tile 1
             "-I" + _HERE, "-I" + _CSRC, "-c"]
 _LINK = [_CLANG, "-shared", "-fPIC", "-Wl,-Bsymbolic"]
 _MAX_JOBS = 16
@@ -100,6 +101,8 @@ def _load(keep, bf16):
         if not key[0]:  # (the fp32 network's entry points that do not return int: emu_mlp_f32.py)
             _libs[key].emuf32_saved_activation_floats.restype = C.c_uint64
             _libs[key].emuf32_n_partials.restype = C.c_uint32
+            for name in ("emuf32f_supported", "emuf32f_n_partials", "emuf32f_max_blocks", "emuf32f_lds_floats"):  # (emu_mlp_f32_fused.py)
+                getattr(_libs[key], name).restype = C.c_uint32
     return _libs[key]
 
 

@@ -2,9 +2,13 @@
 // the SIMT emulator (hip_emu.h) and exposes them to pytest through a flat C interface (host pointers only).  Its parts, one object per
 // kernel family, all linked into ONE library per build variant (emu.py lists them and says which variants there are):
 //   emu_driver_grid.cpp  the grid encoding (csrc/grid_kernels.hip) and the probes of single device functions
-//   emu_driver_mlp.cpp   the network kernels (csrc/mlp_kernels.hip, mlp_train_wave.hip, mlp_train_wide.hip)
+//   emu_driver_mlp.cpp   the network kernels (csrc/mlp_kernels.hip, mlp_train_wave.hip, mlp_train_wide.hip), the fp32 network layer by
+//                        layer (mlp_general_fp32.hip, emuf32_*) and fused (mlp_f32_fused.hip, mlp_f32_fused_backward.hip, emuf32f_*)
 //   emu_driver_misc.cpp  the elementwise, composite and optimizer kernels, the trainer snapshot
 //   emu_driver_half_input.cpp  csrc/half_input_kernels.hip (file-local names that clash with the optimizer kernels')
+// and, in a library of its own (emu_mlp_second_order.py builds it with the same command lines):
+//   emu_driver_mlp_second_order.cpp  the fp32 network's second-order pass, layer by layer (emumso_*) and fused
+//                        (mlp_f32_fused_second_order.hip with the kernels of mlp_f32_fused_backward.hip it launches, emuf32f_*)
 // A NEW ENTRY POINT goes into the part that already includes its kernels, its numpy front-end into emu.py (or the feature module next to
 // it that calls emu.lib()): no new driver file, no new library.  The parts share the library's state (::emu::g, grid_owner_mode(),
 // owner_slice_stats): an entry point sets what it depends on, never relies on a fresh library.  TEST INFRASTRUCTURE ONLY -- see hip_emu.h.

@@ -1,9 +1,12 @@
 // emu_driver_mlp.cpp -- the network's part of the emulator's driver (emu_driver.h): the launchers of csrc/mlp_kernels.hip (which brings
-// csrc/mlp_general.hip along, the 16-bit layer-by-layer network), its fp32 twin csrc/mlp_general_fp32.hip and the register-resident kernels
-// the launchers choose between, as one unit.  TEST INFRASTRUCTURE ONLY -- see hip_emu.h.
+// csrc/mlp_general.hip along, the 16-bit layer-by-layer network), its fp32 twin csrc/mlp_general_fp32.hip, the fused fp32 forward and
+// backward kernels (csrc/mlp_f32_fused.hip, mlp_f32_fused_backward.hip) and the register-resident kernels the launchers choose between, as
+// one unit.  TEST INFRASTRUCTURE ONLY -- see hip_emu.h.
 #include "emu_driver.h"
 #include "../../tiny-cuda-nn_amd/csrc/mlp_kernels.hip"
 #include "../../tiny-cuda-nn_amd/csrc/mlp_general_fp32.hip"
+#include "../../tiny-cuda-nn_amd/csrc/mlp_f32_fused.hip"
+#include "../../tiny-cuda-nn_amd/csrc/mlp_f32_fused_backward.hip"
 #include "../../tiny-cuda-nn_amd/csrc/mlp_train_wave.hip"
 #include "../../tiny-cuda-nn_amd/csrc/mlp_train_wide.hip"
 #include "../../tiny-cuda-nn_amd/csrc/elementwise_kernels.h"  // reduce_sum (emu_driver_misc.cpp holds the kernels)
@@ -157,6 +160,53 @@ int emuf32_mlp_backward(const EmuMlp* e, uint32_t n, const float* params, const 
 		}
 		std::vector<float> workspace(mlp_f32_backward_workspace_bytes(m, n) / sizeof(float), -4321.0f);
 		mlp_f32_backward(nullptr, m, n, params_t.data(), input_fm, hidden, dL_doutput, dL_dinput_fm, grads ? partials.data() : nullptr, workspace.data());
+		if (grads) mlp_f32_finalize_gradients(nullptr, m, np, partials.data(), grads, accumulate != 0);
+	});
+}
+
+// ---- the fused fp32 kernels (mlp_f32_fused.hip, mlp_f32_fused_backward.hip), called directly: mlp_general_fp32.hip compiles its routes to
+// them out under TCNN_HOST_EMU, so the emuf32_* entries above stay the layer-by-layer kernels and the two can be compared.  Arguments as in
+// emuf32_mlp_forward / emuf32_mlp_backward; the saved stack has the same size and layout (emuf32_saved_activation_floats).
+int emuf32f_mlp_forward(const EmuMlp* e, uint32_t n, const float* params, const float* input_fm, float* hidden, float* output, float* trimmed, uint32_t dims,
+                        uint32_t stride_i, uint32_t stride_j) {
+	return emu_call(__func__, [&] {
+		MlpF32Output t;
+		if (trimmed) t = {trimmed, dims, stride_i, stride_j};
+		mlp_f32_fused_forward(nullptr, make_mlp(e), n, params, input_fm, hidden, trimmed ? nullptr : output, t);
+	});
+}
+
+uint32_t emuf32f_supported(const EmuMlp* e, uint32_t n) { return mlp_f32_fused_supported(make_mlp(e), n) ? 1u : 0u; }
+uint32_t emuf32f_n_partials(const EmuMlp* e, uint32_t n) { return mlp_f32_fused_n_partials(make_mlp(e), n); }
+uint32_t emuf32f_max_blocks() { return F32F_MAX_BLOCKS; }
+// floats of LDS: 0 the forward matrices resident, 1 / 2 the transposed ones with / without the input matrix (dL_dinput wanted or not),
+// 3 what fits (F32F_RESIDENT_LDS_BYTES): a pass whose figure is above it stages one matrix at a time
+uint32_t emuf32f_lds_floats(const EmuMlp* e, uint32_t which) {
+	const MlpMeta m = make_mlp(e);
+	switch (which) {
+		case 0: return f32f_resident_floats(m);
+		case 1: return f32b_resident_floats(m, true);
+		case 2: return f32b_resident_floats(m, false);
+		default: return F32F_RESIDENT_LDS_BYTES / (uint32_t)sizeof(float);
+	}
+}
+
+int emuf32f_mlp_backward(const EmuMlp* e, uint32_t n, const float* params, const float* input_fm, const float* hidden, const float* dL_doutput, float* dL_dinput_fm, float* grads,
+                         int accumulate, const float* output) {
+	return emu_call(__func__, [&] {
+		const MlpMeta m = make_mlp(e);
+		std::vector<float> params_t(m.n_params(), -777.0f);
+		mlp_f32_transpose_weights(nullptr, m, params, params_t.data());
+		const uint32_t np = mlp_f32_fused_n_partials(m, n);
+		std::vector<float> partials(grads ? (size_t)np * m.n_params() : 0, -12345.0f), dpre;
+		if (m.output_activation != (uint32_t)Activation::None) {
+			if (!output) throw std::runtime_error("output required");
+			dpre.resize((size_t)n * m.padded_out);
+			mlp_f32_output_activation_backward(nullptr, m, n, output, dL_doutput, dpre.data());
+			dL_doutput = dpre.data();
+		}
+		std::vector<float> workspace(mlp_f32_backward_workspace_bytes(m, n) / sizeof(float), -4321.0f);
+		mlp_f32_fused_backward(nullptr, m, n, params_t.data(), input_fm, hidden, dL_doutput, dL_dinput_fm, grads ? partials.data() : nullptr, workspace.data());
 		if (grads) mlp_f32_finalize_gradients(nullptr, m, np, partials.data(), grads, accumulate != 0);
 	});
 }

@@ -13,7 +13,10 @@ constexpr uint32_t F32F_THREADS = 512;
 constexpr uint32_t F32F_WAVE_SAMPLES = 32;                 // two 16-column sample tiles
 constexpr uint32_t F32F_PAD = 8;                           // floats between the end of a weight row and the next row in LDS
 constexpr uint32_t F32F_RESIDENT_LDS_BYTES = 128u << 10;   // of the CU's 160 KiB
-constexpr uint32_t F32F_MAX_BLOCKS = 512;                  // two workgroups per CU where LDS and registers allow
+#ifndef TCNN_F32F_MAX_BLOCKS
+#define TCNN_F32F_MAX_BLOCKS 512                           // (the host emulator's build sets 2: uneven shares of the persistent tile loop)
+#endif
+constexpr uint32_t F32F_MAX_BLOCKS = TCNN_F32F_MAX_BLOCKS; // two workgroups per CU where LDS and registers allow
 static_assert(F32F_THREADS / WAVE * F32F_WAVE_SAMPLES == MLP_F32_FUSED_TILE, "a workgroup's waves cover its tile");
 
 // one weight matrix [rows][K], global -> LDS rows of K + F32F_PAD floats, 16 bytes per thread and step

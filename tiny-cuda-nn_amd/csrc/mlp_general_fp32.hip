@@ -58,7 +58,7 @@ void mlp_f32_forward(hipStream_t stream, const MlpMeta& m, uint32_t n, const flo
 	g32_check_shape(m, n);
 	if (trimmed.out && (hidden || output)) throw std::runtime_error("mlp_f32_forward: the trimmed output is for inference, in place of the padded one");
 	if (trimmed.out && (trimmed.dims == 0 || trimmed.dims > m.padded_out)) throw std::runtime_error("mlp_f32_forward: the trimmed output has at most padded_out columns");
-#if !defined(TCNN_HOST_EMU)  // (the emulator's drivers include this unit alone: the layer-by-layer kernels)
+#if !defined(TCNN_HOST_EMU)  // (on the host emulator this unit stays the layer-by-layer kernels; its drivers call the fused units' entry points themselves)
 	if (g_fp32_fused_network.load() != 0 && mlp_f32_fused_supported(m, n)) return mlp_f32_fused_forward(stream, m, n, params, input, hidden, output, trimmed);
 #endif
 	gen_forward<float>(stream, m, n, params, input, hidden, output, trimmed);
