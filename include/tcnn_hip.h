@@ -503,6 +503,21 @@ int tcnn_module_fp32_fused_backward(const tcnn_module_t* m, uint32_t n_elements)
 int tcnn_set_fp32_fused_second_order(int enable);
 int tcnn_get_fp32_fused_second_order(void);
 int tcnn_module_fp32_fused_second_order(const tcnn_module_t* m, uint32_t n_elements);
+/* Parameter gradients of an fp32 grid encoding (bare, nested in a Composite, or in front of an fp32 network), process-wide, default 1: the
+ * owner pass (csrc/grid_backward_f32.hip).  Every corner's fp32 term is derived once, binned by the slice of the table that owns it and
+ * summed there in 64-bit integers on a quantum per gradient value, q_v = 2^(e_v + ceil(log2 n) + D - 62), where 2^(e_v - 1) <= max |term| <
+ * 2^e_v over the terms that reach the value in this call of n samples (never coarser than q_l, the same with the level's max |dL_dy|): no
+ * floating-point atomics on global memory, no memset of those levels, and a gradient that does not depend on the order of the samples.
+ * Against the exact sum of the fp32 terms a value that `hits` terms reach is off by at most hits * q_v / 2 and one rounding to fp32;
+ * Accumulate adds that sum to the stored value once per entry.  A level of zeros gives zeros;
+ * NaN and Inf in dL_dy reach the entries they touch as NaN / Inf, as a floating-point sum would carry them.  0: the reference's formulation
+ * at every shape (a memset and one fp32 global atomic per corner and feature), which is also what stochastic interpolation, levels outside
+ * the plan and the second-order scatter run at either setting.  tcnn_module_fp32_grid_backward: 1 if a backward call of n_elements on this
+ * module would send at least one grid level through the owner pass now; 0 for 16-bit modules, modules without a grid, stochastic grids
+ * and with the switch off. */
+int tcnn_set_fp32_grid_backward(int enable);
+int tcnn_get_fp32_grid_backward(void);
+int tcnn_module_fp32_grid_backward(const tcnn_module_t* m, uint32_t n_elements);
 /* Accumulator form of the bucket owners in mode 3, process-wide (same bits from all three): 0 = packed (default: both features of a
  * payload word in one 64-bit LDS word, half the LDS atomics and half the LDS; slices whose sums could leave int32 are redone wide),
  * 1 = 64-bit fixed point per value throughout, 2 = the packed kernel with every slice through its wide redo (tests). */

@@ -221,6 +221,18 @@ int tcnn_module_fp32_fused_network(const tcnn_module_t* m, uint32_t n_elements) 
 int tcnn_module_fp32_fused_backward(const tcnn_module_t* m, uint32_t n_elements) {
 	return m && m->fp32_network() && mlp_f32_backward_is_fused(m->md.net.mlp, n_elements) ? 1 : 0;
 }
+// what the encoding's backward pass decides for a backward call of n_elements on this module: does at least one level of a grid of its
+// encoding go through the owner pass of fp32 grids (host arithmetic on the plan, grid_backward_plan.h make_f32_backward_plan)?
+int tcnn_module_fp32_grid_backward(const tcnn_module_t* m, uint32_t n_elements) {
+	if (!m || !m->fp32_io || g_fp32_grid_backward.load() == 0 || n_elements == 0) return 0;
+	const EncodingDesc& e = m->md.enc;
+	if (e.is_grid()) return e.n_params > 0 && grid_backward_f32_owner_levels(e.grid, n_elements) > 0 ? 1 : 0;
+	if (!e.is_composite()) return 0;
+	for (const EncodingDesc& g : e.nested) {
+		if (g.is_grid() && g.n_params > 0 && grid_backward_f32_owner_levels(g.grid, n_elements) > 0) return 1;
+	}
+	return 0;
+}
 // what mlp_f32_backward_backward decides for a backward_backward_input call of n_elements on this module
 int tcnn_module_fp32_fused_second_order(const tcnn_module_t* m, uint32_t n_elements) {
 	return m && m->fp32_network() && mlp_f32_backward_backward_is_fused(m->md.net.mlp, n_elements) ? 1 : 0;

@@ -67,9 +67,10 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_backward_atomic(const Gri
 
 template <uint32_t D, uint32_t F>
 __global__ void __launch_bounds__(GRID_THREADS) k_grid_backward_atomic_f32(const GridMeta meta, const GridIO io, const float* __restrict__ dL_dy,
-                                                                            float* __restrict__ grid_gradient) {
+                                                                            float* __restrict__ grid_gradient, const LevelMask skip) {
 	uint32_t level, tile;
 	if (!grid_work_item(meta.n_levels, div_round_up(io.n, GRID_TILE), level, tile)) return;
+	if (skip.test(level)) return;  // the owner pass has this level (grid_backward_f32.hip)
 	if (!io.max_level && level_is_off<false>(meta, level, F)) return;
 	const Level<D> lv = make_level<D>(meta, level);
 	float* __restrict__ grad = grid_gradient + (size_t)meta.offset[level] * F;
@@ -439,17 +440,52 @@ void grid_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, c
 }
 
 // ---- fp32 encodings (GridEncodingTemplated<float>) ----
-void grid_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, float* grid_gradient, bool accumulate) {
+// Which levels a first-order backward of n samples sends through the owner pass when its caller brings the workspace: none for stochastic
+// interpolation (make_f32_backward_plan), and none on the host emulator, which does not build that pass yet.
+static F32BackwardPlan f32_backward_plan(const GridMeta& meta, uint32_t n) {
+#if defined(TCNN_HOST_EMU)
+	return F32BackwardPlan();
+#else
+	return make_f32_backward_plan(meta, n);
+#endif
+}
+size_t grid_backward_f32_workspace_bytes(const GridMeta& meta, uint32_t n) { return f32_backward_plan(meta, n).workspace_bytes; }
+uint32_t grid_backward_f32_owner_levels(const GridMeta& meta, uint32_t n) { return f32_backward_plan(meta, n).owners.n_levels; }
+
+void grid_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, float* grid_gradient, bool accumulate,
+                   const GridBackwardWorkspace& ws) {
 	if (io.n == 0) return;
 	if (!grid_gradient) throw std::runtime_error("grid_backward: missing gradient buffer");
-	const size_t n_params = (size_t)meta.offset[meta.n_levels] * meta.n_feat;
-	if (!accumulate) {  // grid.h:865-867
-		if (hipMemsetAsync(grid_gradient, 0, n_params * sizeof(float), stream) != hipSuccess) throw std::runtime_error("grid_backward: memset failed");
+	// the owner pass takes the levels of its plan when the caller brought its workspace; the second-order scatter (io.ddx) stays on the atomics
+	F32BackwardPlan bp;
+	if (!io.ddx && ws.scratch) {
+		bp = f32_backward_plan(meta, io.n);
+		if (ws.scratch_bytes < bp.workspace_bytes) throw std::runtime_error("grid_backward: workspace too small for the fp32 owner pass");
 	}
+	bool atomic_levels = false;
+	for (uint32_t l = 0; l < meta.n_levels; ++l) atomic_levels = atomic_levels || !bp.taken.test(l);
+	if (!accumulate && atomic_levels) {  // grid.h:865-867: atomically updated levels start from zero, the owners store their levels whole
+		for (uint32_t a = 0; a < meta.n_levels;) {  // one memset per run of such levels (the whole table where the owner pass is off)
+			uint32_t b = a;
+			while (b < meta.n_levels && !bp.taken.test(b)) ++b;
+			if (b > a && hipMemsetAsync(grid_gradient + (size_t)meta.offset[a] * meta.n_feat, 0, (size_t)(meta.offset[b] - meta.offset[a]) * meta.n_feat * sizeof(float), stream) != hipSuccess) {
+				throw std::runtime_error("grid_backward: memset failed");
+			}
+			a = b + 1;
+		}
+	}
+#if !defined(TCNN_HOST_EMU)
+	if (bp.owners.n_levels) {
+		if (ws.phase_hook) ws.phase_hook(ws.hook_user, 1, 1);
+		launch_f32_owner_backward(stream, meta, io, bp, dL_dy, ws.scratch, grid_gradient, accumulate);
+		if (ws.phase_hook) ws.phase_hook(ws.hook_user, 1, 0);
+	}
+#endif
+	if (!atomic_levels) return;
 	// second-order scatter (io.ddx set): d(dy_dx)/d(grid) == 0 without interpolation (grid.h:422-425)
 	if (io.ddx && meta.interp == (uint32_t)InterpolationType::Nearest) return;
 	const uint32_t blocks = grid_n_blocks(meta.n_levels, io.n);
-	grid_dispatch(meta, [&](auto D, auto F) { TCNN_LAUNCH((k_grid_backward_atomic_f32<D, F>), dim3(blocks), dim3(GRID_THREADS), 0, stream, meta, io, dL_dy, grid_gradient); });
+	grid_dispatch(meta, [&](auto D, auto F) { TCNN_LAUNCH((k_grid_backward_atomic_f32<D, F>), dim3(blocks), dim3(GRID_THREADS), 0, stream, meta, io, dL_dy, grid_gradient, bp.taken); });
 }
 
 }  // namespace tcnn_hip

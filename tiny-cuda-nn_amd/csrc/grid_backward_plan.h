@@ -289,6 +289,108 @@ inline BackwardPlan make_backward_plan(const GridMeta& meta, uint32_t n, bool pa
 	return bp;
 }
 
+// ---- fp32 encodings: the plan of the owner-computed backward (grid_backward_f32.hip) ---------------------------------------------------
+// The same cut of a level's table into slices that one workgroup keeps in LDS (MAX_BUCKETS_PER_LEVEL slices and MAX_BUCKET_LEVELS levels at
+// the most), with another record and another queue discipline.  A record is ONE corner: {entry index within its slice, F fp32 terms}, 1 + F
+// words -- a 32-bit payload per feature leaves no room to pair two corners in a 16-byte store.  The queues are sized EXACTLY: a counting
+// launch derives every record's slice first, a scan turns the counts into each slice's run inside one array of n * corners records per level,
+// and the scatter fills the runs.  No capacity guess, no overflow list, and clustered samples cost time, never a fallback.  A slice has
+// 2^shift entries, at most F32_OWNER_VALUES / F, chosen per level: a small table (every sample lands in it) is cut finer, down to 8 entries,
+// until a slice expects about F32_OWNER_RECORDS records -- the samples of a slice are never split, so an entry has ONE owner and no owner
+// ever combines sums with another.
+//
+// The quantum.  The owners sum integers: a term t (corner weight x dL_dy, formed in fp32 as k_grid_backward_atomic_f32 forms it) enters as
+// round-to-nearest-even(t / q), with one power of two q per gradient VALUE (entry and feature) and call:
+//     q_v = 2^(e_v + ceil(log2 n) + D - 62),    2^(e_v - 1) <= max |t| < 2^e_v over the finite terms that reach the value
+// The owner finds the maxima in a first pass over its run (integer LDS maxima on the bits of |t|: the same in any order) and sums in a
+// second.  |t / q_v| < 2^(62 - ceil(log2 n) - D) and a value receives at most n * 2^D terms, so every sum stays inside 2^62: int64 with one
+// spare bit.  The sum is exact and the same in any order; it is converted to fp32 once, at the store.  Against the exact sum of the fp32
+// terms a value that `hits` terms reach is off by at most hits * q_v / 2 plus that one conversion (half an ulp of the result).  Weights are
+// at most one, so q_v <= q_l = 2^(e_l + ceil(log2 n) + D - 62) with 2^(e_l - 1) <= max |dL_dy| < 2^e_l over the level's features and all n
+// samples -- the per-level bound the tests compute -- and q_v is 2^-(61 - ceil(log2 n) - D) of the value's own largest term or finer
+// (2^-40 at 2^18 samples and D = 3): a value that only small terms reach keeps their bits whatever else the level carries.
+// A value that no term or only zeros reach: +0.  NaN and Inf: a term that is not finite (Inf or NaN dL_dy times any weight) is left out of
+// the maximum and sets a flag on its value instead of entering the sum; at the store a flagged value becomes what a floating-point sum in any
+// order would have given -- NaN if a NaN or both infinities were seen, else the infinity seen -- so the owners propagate what the atomic
+// kernel produces and the other values keep their exact sums.
+constexpr uint32_t F32_SCATTER_THREADS = 256;
+constexpr uint32_t F32_RECORDS_PER_LANE = 16;   // a lane of the counting / scatter launches holds 16 >> D samples: 16 records
+constexpr uint32_t F32_OWNER_VALUES = 8192;     // gradient values of a slice at the most: a 64-bit sum, a 32-bit maximum and 4 flag bits each
+constexpr uint32_t F32_OWNER_LDS_BYTES = F32_OWNER_VALUES * 12u + F32_OWNER_VALUES / 2u;
+constexpr uint32_t F32_OWNER_RECORDS = 32768;   // records an owner is meant to see (the 16-bit plan chunks its small tables to the same)
+constexpr uint32_t F32_FLAG_POS_INF = 1u, F32_FLAG_NEG_INF = 2u, F32_FLAG_NAN = 4u;
+TCNN_HOST_DEVICE constexpr uint32_t f32_record_words(uint32_t F) { return 1u + F; }
+
+// what the kernels of the pass read (by value); offsets are 32-bit words from the start of the control block at the workspace's head
+struct F32OwnerPlan {
+	uint32_t n_levels;        // levels the pass takes (slot j = 0 .. n_levels - 1)
+	uint32_t log2_terms;      // ceil(log2 n) + D: the quantum's headroom
+	uint32_t tiles;           // sample tiles of the counting / scatter launches
+	uint32_t n_slices_total, n_queue_records;
+	uint32_t count_base, start_base, cursor_base, control_words;
+	uint8_t level[MAX_BUCKET_LEVELS];
+	uint8_t shift[MAX_BUCKET_LEVELS];                // log2(entries per slice) of slot j
+	uint32_t n_slices[MAX_BUCKET_LEVELS];
+	uint32_t slice_base[MAX_BUCKET_LEVELS + 1];      // first slice of slot j among all slices: also the first owner workgroup
+};
+struct LevelMask {  // bit l: level l is not this launch's
+	uint32_t bits[MAX_N_LEVELS / 32];
+	TCNN_HOST_DEVICE bool test(uint32_t l) const { return (bits[l >> 5] >> (l & 31u)) & 1u; }
+};
+struct F32BackwardPlan {
+	F32OwnerPlan owners = {};
+	LevelMask taken = {};         // levels of the owner pass; the others stay on k_grid_backward_atomic_f32
+	size_t queue_offset = 0, workspace_bytes = 0;  // control block at offset 0 of the workspace, then the queues
+};
+
+// Which levels of an fp32 grid the owner pass takes for a first-order backward of n samples, and where its state lies.  Stochastic
+// interpolation (one unweighted update per sample and level) stays on the atomic kernel, as in the 16-bit plan; so does the second-order
+// scatter (the caller does not plan it: its records follow another magnitude law).
+inline F32BackwardPlan make_f32_backward_plan(const GridMeta& meta, uint32_t n) {
+	F32BackwardPlan bp;
+	if (n == 0 || meta.stochastic != 0u) return bp;
+	F32OwnerPlan& op = bp.owners;
+	const uint32_t F = meta.n_feat, D = meta.n_dims;
+	uint32_t max_shift = 0;
+	while ((2u << max_shift) <= F32_OWNER_VALUES / F) ++max_shift;
+	const uint32_t n_corners = meta.interp == (uint32_t)InterpolationType::Nearest ? 1u : (1u << D);
+	uint32_t log2_n = 0;
+	while (((uint64_t)1 << log2_n) < n) ++log2_n;
+	op.log2_terms = log2_n + D;
+	op.tiles = div_round_up(n, F32_SCATTER_THREADS * (F32_RECORDS_PER_LANE >> D));
+	const uint64_t level_records = (uint64_t)n * n_corners;
+	const uint32_t wanted_slices = (uint32_t)std::min<uint64_t>(div_round_up<uint64_t>(level_records, F32_OWNER_RECORDS), MAX_BUCKETS_PER_LEVEL);
+	uint64_t n_records = 0;
+	for (uint32_t l = 0; l < meta.n_levels; ++l) {
+		const uint32_t entries = meta.offset[l + 1] - meta.offset[l];
+		uint32_t shift = max_shift;
+		while (shift > 3u && div_round_up(entries, 1u << shift) < wanted_slices && div_round_up(entries, 1u << (shift - 1u)) <= MAX_BUCKETS_PER_LEVEL) --shift;
+		const uint32_t n_slices = div_round_up(entries, 1u << shift);
+		if (entries == 0 || op.n_levels == MAX_BUCKET_LEVELS || n_slices > MAX_BUCKETS_PER_LEVEL || n_records + level_records > 0xFFFFFFFFull) continue;
+		const uint32_t j = op.n_levels++;
+		op.level[j] = (uint8_t)l;
+		op.shift[j] = (uint8_t)shift;
+		op.n_slices[j] = n_slices;
+		op.slice_base[j] = op.n_slices_total;
+		op.n_slices_total += n_slices;
+		n_records += level_records;
+		bp.taken.bits[l >> 5] |= 1u << (l & 31u);
+	}
+	if (op.n_levels == 0) return bp;
+	op.slice_base[op.n_levels] = op.n_slices_total;
+	op.n_queue_records = (uint32_t)n_records;
+	op.count_base = 0;
+	op.start_base = op.n_slices_total;
+	op.cursor_base = 2u * op.n_slices_total;
+	op.control_words = next_multiple(3u * op.n_slices_total, 4u);
+	bp.queue_offset = next_multiple<size_t>((size_t)op.control_words * sizeof(uint32_t), 256);
+	bp.workspace_bytes = bp.queue_offset + next_multiple<size_t>(n_records * f32_record_words(F) * sizeof(uint32_t), 256);
+	return bp;
+}
+// the launches of that pass over the taken levels (grid_backward_f32.hip): clear, count, scan, scatter, owners
+void launch_f32_owner_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const F32BackwardPlan& bp, const float* dL_dy, void* workspace,
+                               float* grid_gradient, bool accumulate);
+
 // The two passes of the bucketed mode, each launched from the file that holds its kernel (grid_backward_scatter.hip, grid_backward_owner.hip);
 // grid_backward.hip runs them in turn.  `counters`, `queues`, `overflow`: the three parts of the GridBackwardWorkspace.
 void launch_bucket_scatter(hipStream_t stream, const GridMeta& meta, const GridIO& io, const BucketPlan& plan, const half_t* dL_dy, uint32_t* counters,

@@ -13,6 +13,7 @@
 //     the slice -- exact, order-independent, no float atomics, no memset (grid_backward_owner.*).  Levels the bucket plan does not take
 //     and the SlicedF32 / SlicedF16 modes (A/B measurements) run the sliced owner-computes kernel, which re-derives the corners per
 //     slice; the Atomic mode is the reference's formulation and the fallback for stochastic interpolation (grid_backward.hip).
+//   * backward of fp32 encodings: the same idea with fp32 records, exactly sized queues and a per-level quantum (grid_backward_f32.hip).
 //   * shared by all of them: grid_device.h (level / cell arithmetic), grid_backward_plan.h (the host plan of the backward passes).
 #pragma once
 #include "tcnn_device.h"
@@ -99,10 +100,25 @@ void grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_feature
                          uint32_t dx_stride_d);
 
 // ---- fp32 encodings: GridEncodingTemplated<float> (cpp_api.cu:165-168), the overloads on float.  Parameters / encoded features / gradients
-// fp32, the reference's formulation (fp32 fma interpolation, one fp32 global atomic per corner and feature); same GridIO addressing as above.
-// That backward has one formulation: no mode, no LDS budget, no workspace.
+// fp32 (fp32 fma interpolation); same GridIO addressing as above.
+// That backward has two formulations, chosen per level:
+//   * the owner pass (grid_backward_f32.hip), for a caller that brings `workspace.scratch` of grid_backward_f32_workspace_bytes() bytes (device
+//     memory the call may scribble on; nothing is kept in it between calls, `counters` and the mode / LDS budget of the 16-bit form are not
+//     used): every corner's fp32 term -- formed as the atomic kernel forms it -- is derived once, binned by the table slice that owns it and
+//     summed there in 64-bit integers on a quantum per gradient value, q_v = 2^(e_v + ceil(log2 n) + D - 62), 2^(e_v - 1) <= max |term| < 2^e_v
+//     over the terms that reach the value -- never coarser than q_l, the same with max |dL_dy| over the level (grid_backward_plan.h states the
+//     rule and what it implies: at most hits * q_v / 2 off the exact sum of the terms, then one rounding to fp32).  No floating-point
+//     global atomics, no memset of these levels, the same bits for any order of the samples; Accumulate adds
+//     the sum to the stored value once per entry.  It takes every level of the first 32 that has at most 4096 slices, while the records of
+//     the taken levels stay below 2^32;
+//   * the reference's (k_grid_backward_atomic_f32: a memset of the levels it runs under Overwrite, one fp32 global atomic per corner and
+//     feature) for the other levels, for stochastic interpolation, for the second-order scatter (io.ddx set: its records follow another
+//     magnitude law) and for a caller without a workspace.
 void grid_forward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* params, float* out, float* dy_dx = nullptr);
-void grid_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, float* grid_gradient, bool accumulate);
+size_t grid_backward_f32_workspace_bytes(const GridMeta& meta, uint32_t n);  // 0: no level of this grid goes through the owner pass
+uint32_t grid_backward_f32_owner_levels(const GridMeta& meta, uint32_t n);   // levels that would (host arithmetic on the plan)
+void grid_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, float* grid_gradient, bool accumulate,
+                   const GridBackwardWorkspace& workspace = GridBackwardWorkspace());
 void grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_features, const GridIO& io, const float* dL_dy, const float* dy_dx, float* dL_dx,
                          uint32_t dx_stride_i, uint32_t dx_stride_d);
 

@@ -96,7 +96,7 @@ template <typename T>
 void encoding_forward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, uint32_t n, const float* input, const T* enc_params, T* out,
                       uint32_t stride_k, uint32_t stride_i, ForwardCtx* ctx = nullptr, bool prepare_input_gradients = false);
 // the encoding's share of the backward pass: dL_denc has element (feature k, sample i) at [k * stride_k + i * stride_i]; dL_dparams is the
-// model's (the encoding's behind the network's).  The fp32 grid backward has one formulation: budget and groups are the 16-bit one's.
+// model's (the encoding's behind the network's).  The fp32 grid backward takes its own workspace (tcnn_set_fp32_grid_backward): budget and groups are the 16-bit one's.
 // The caller has been through begin_backward (model_backward, the fp32 module entry) or made `ctx` itself in this call (the fused step).
 template <typename T>
 void encoding_backward(hipStream_t stream, Profiler* profiler, const Model& md, const IoLayout& layout, const ForwardCtx& ctx, uint32_t n, float* dL_dinput, const T* dL_denc,

@@ -537,13 +537,22 @@ void grid_backward_with_workspace(hipStream_t stream, const GridSlice& s, const 
 }
 
 // One grid's parameter gradients in the pass's value type.  16-bit: the chosen backward mode with its LDS budget and workspace, level groups
-// with the `ready` callback, the profiler's stages.  fp32: the reference's one formulation has none of them.
+// with the `ready` callback, the profiler's stages.  fp32: the owner pass's workspace out of the stream's scratch cache while
+// tcnn_set_fp32_grid_backward is on (without one, grid_backward runs the reference's atomic formulation at every level).
 static void grid_parameter_gradients(hipStream_t stream, PhaseTimer& timer, const GridSlice& s, const half_t* dL_dy, half_t* grid_gradient, bool accumulate, uint32_t lds_level_budget,
                                      const LevelGroups* groups, size_t first_param) {
 	grid_backward_with_workspace(stream, s, dL_dy, grid_gradient, accumulate, (GridBackwardMode)g_grid_backward_mode.load(), lds_level_budget, &timer, groups, first_param);
 }
 static void grid_parameter_gradients(hipStream_t stream, PhaseTimer&, const GridSlice& s, const float* dL_dy, float* grid_gradient, bool accumulate, uint32_t, const LevelGroups*, size_t) {
-	grid_backward(stream, s.grid, s.io, dL_dy, grid_gradient, accumulate);
+	GridBackwardWorkspace ws;
+	Scratch queues;
+	if (g_fp32_grid_backward.load() != 0) ws.scratch_bytes = grid_backward_f32_workspace_bytes(s.grid, s.io.n);
+	if (ws.scratch_bytes) {
+		queues = Scratch(stream, ws.scratch_bytes);
+		ws.scratch = queues.ptr;
+		ws.scratch_bytes = queues.bytes;
+	}
+	grid_backward(stream, s.grid, s.io, dL_dy, grid_gradient, accumulate, ws);
 }
 
 // The encoding's share of the backward pass, from dL/d(encoded input) -- the feature-major matrix the network kernels wrote, or a bare

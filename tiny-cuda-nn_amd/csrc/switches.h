@@ -35,5 +35,8 @@ extern std::atomic<int> g_fp32_fused_backward;
 // (mlp_f32_fused_second_order.hip, default), 0 = the layer-by-layer launches (tcnn_set_fp32_fused_second_order).  Read together with the
 // two switches above: either of them at 0 turns the fused second-order pass off as well.
 extern std::atomic<int> g_fp32_fused_second_order;
+// parameter gradients of an fp32 grid encoding: 1 = the owner pass on the levels its plan takes (grid_backward_f32.hip, default), 0 = the
+// reference's atomic kernel at every shape (tcnn_set_fp32_grid_backward; A/B runs, tests, the earlier bits)
+extern std::atomic<int> g_fp32_grid_backward;
 
 }  // namespace tcnn_hip

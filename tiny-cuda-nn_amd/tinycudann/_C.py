@@ -215,6 +215,9 @@ _sig("tcnn_module_fp32_fused_backward", _i, _vp, _u32)
 _sig("tcnn_set_fp32_fused_second_order", _i, _i)
 _sig("tcnn_get_fp32_fused_second_order", _i)
 _sig("tcnn_module_fp32_fused_second_order", _i, _vp, _u32)
+_sig("tcnn_set_fp32_grid_backward", _i, _i)
+_sig("tcnn_get_fp32_grid_backward", _i)
+_sig("tcnn_module_fp32_grid_backward", _i, _vp, _u32)
 _sig("tcnn_set_grid_owner_mode", _i, _i)
 _sig("tcnn_get_grid_owner_mode", _i)
 _sig("tcnn_grid_owner_wide_slices", _i, C.POINTER(C.c_uint64))
@@ -358,6 +361,16 @@ def set_fp32_fused_second_order(enable):
     weight-gradient kernels (default) / one launch per layer, chain and matrix.  set_fp32_fused_network(False) and
     set_fp32_fused_backward(False) turn the fused second-order pass off as well."""
     _check(_lib.tcnn_set_fp32_fused_second_order(int(bool(enable))))
+
+
+def get_fp32_grid_backward():
+    return bool(_lib.tcnn_get_fp32_grid_backward())
+
+
+def set_fp32_grid_backward(enable):
+    """Parameter gradients of fp32 grid encodings, process-wide: the owner pass (default: exact 64-bit sums on a per-level quantum, no
+    floating-point global atomics, independent of the order of the samples) / the reference's atomic kernel at every shape."""
+    _check(_lib.tcnn_set_fp32_grid_backward(int(bool(enable))))
 
 
 def get_grid_owner_mode():
@@ -519,6 +532,10 @@ class Module:
     def fp32_fused_second_order(self, n):
         """1 if a bwd_bwd_input call of n rows on this module would run the fused fp32 second-order kernels now (set_fp32_fused_second_order), else 0."""
         return int(_lib.tcnn_module_fp32_fused_second_order(self._h, int(n)))
+
+    def fp32_grid_backward(self, n):
+        """1 if a backward call of n rows on this module would send at least one grid level through the fp32 owner pass now (set_fp32_grid_backward), else 0."""
+        return int(_lib.tcnn_module_fp32_grid_backward(self._h, int(n)))
 
     def _takes_half(self, input):
         return input.dtype != torch.float32 and input.dtype == self._torch_param_dtype() and self.supports_half_input()
@@ -791,6 +808,7 @@ class ExtModule:
     fp32_fused_network = Module.fp32_fused_network
     fp32_fused_backward = Module.fp32_fused_backward
     fp32_fused_second_order = Module.fp32_fused_second_order
+    fp32_grid_backward = Module.fp32_grid_backward
 
 
 def ext_apply(module, x, params, loss_scale):
