@@ -518,6 +518,16 @@ int tcnn_module_fp32_fused_second_order(const tcnn_module_t* m, uint32_t n_eleme
 int tcnn_set_fp32_grid_backward(int enable);
 int tcnn_get_fp32_grid_backward(void);
 int tcnn_module_fp32_grid_backward(const tcnn_module_t* m, uint32_t n_elements);
+/* Forward pass of an fp32 grid encoding (bare, nested in a Composite, or in front of an fp32 network), with or without the input
+ * gradients' dy_dx, process-wide, default 1: the level-major tiled gather (csrc/grid_forward_f32.hip) -- the (level, sample tile) items cut
+ * into eight runs of equal cost, one per XCD, a thread issuing every corner load of its samples (4 / 8 / 16-byte accesses) before the first
+ * use, dy_dx stored as one 8 / 12 / 16-byte access per feature.  0: one thread per (sample, level) at every form, which is also what a
+ * per-sample max_level array, Nearest interpolation and parameters off a 16-byte boundary run at either setting.  The same bits either way.
+ * tcnn_module_fp32_grid_forward: 1 if a forward call of n_elements on this module would run the tiled gather on a grid of its encoding now;
+ * 0 for 16-bit modules, modules without a grid, Nearest, a module with a per-sample max_level array set and with the switch off. */
+int tcnn_set_fp32_grid_forward(int enable);
+int tcnn_get_fp32_grid_forward(void);
+int tcnn_module_fp32_grid_forward(const tcnn_module_t* m, uint32_t n_elements);
 /* Accumulator form of the bucket owners in mode 3, process-wide (same bits from all three): 0 = packed (default: both features of a
  * payload word in one 64-bit LDS word, half the LDS atomics and half the LDS; slices whose sums could leave int32 are redone wide),
  * 1 = 64-bit fixed point per value throughout, 2 = the packed kernel with every slice through its wide redo (tests). */

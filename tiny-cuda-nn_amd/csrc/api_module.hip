@@ -233,6 +233,18 @@ int tcnn_module_fp32_grid_backward(const tcnn_module_t* m, uint32_t n_elements) 
 	}
 	return 0;
 }
+// what the fp32 grid_forward decides for a forward call of n_elements on this module, with or without dy_dx: does a grid of its encoding run
+// the tiled gather (grid_forward_f32.hip)?  (The per-sample max_level array belongs to a lone grid; nested grids have none.)
+int tcnn_module_fp32_grid_forward(const tcnn_module_t* m, uint32_t n_elements) {
+	if (!m || !m->fp32_io || n_elements == 0) return 0;
+	const EncodingDesc& e = m->md.enc;
+	if (e.is_grid()) return grid_forward_f32_is_tiled(e.grid, e.max_level_gpu != nullptr) ? 1 : 0;
+	if (!e.is_composite()) return 0;
+	for (const EncodingDesc& g : e.nested) {
+		if (g.is_grid() && grid_forward_f32_is_tiled(g.grid, false)) return 1;
+	}
+	return 0;
+}
 // what mlp_f32_backward_backward decides for a backward_backward_input call of n_elements on this module
 int tcnn_module_fp32_fused_second_order(const tcnn_module_t* m, uint32_t n_elements) {
 	return m && m->fp32_network() && mlp_f32_backward_backward_is_fused(m->md.net.mlp, n_elements) ? 1 : 0;

@@ -45,6 +45,7 @@ std::atomic<int> g_fp32_fused_network{1};
 std::atomic<int> g_fp32_fused_backward{1};
 std::atomic<int> g_fp32_fused_second_order{1};
 std::atomic<int> g_fp32_grid_backward{1};
+std::atomic<int> g_fp32_grid_forward{1};
 
 }  // namespace tcnn_hip
 
@@ -178,6 +179,11 @@ int tcnn_set_fp32_fused_backward(int enable) {
 int tcnn_get_fp32_grid_backward(void) { return g_fp32_grid_backward.load(); }
 int tcnn_set_fp32_grid_backward(int enable) {
 	g_fp32_grid_backward.store(enable != 0 ? 1 : 0);
+	return TCNN_OK;
+}
+int tcnn_get_fp32_grid_forward(void) { return g_fp32_grid_forward.load(); }
+int tcnn_set_fp32_grid_forward(int enable) {
+	g_fp32_grid_forward.store(enable != 0 ? 1 : 0);
 	return TCNN_OK;
 }
 int tcnn_get_fp32_fused_second_order(void) { return g_fp32_fused_second_order.load(); }

@@ -1,43 +1,12 @@
 // grid_forward.hip -- the gathers: the tiled forward that training and inference run, the reference-form forward with dy_dx, the fp32
-// encoding's forward and the index helper; the tiled gather's work plan and the launchers.
-#include "grid_device.h"
-
-#include <algorithm>
-#include <cmath>
+// encoding's reference-form forward and the index helper, and the launchers.  grid_forward_plan.h: the tiled gather's work plan.
+#include "grid_forward_plan.h"
 
 namespace tcnn_hip {
 
 // =============================================================================================
 // forward (grid.h:49-212)
 // =============================================================================================
-// d(feature)/d(position) of one sample (grid.h:172-211): along every dimension the differences of the corner pairs, weighted by the
-// other dimensions' interpolation weights.  value(corner, f): feature f of corner `corner` as float.
-template <uint32_t D, uint32_t F, typename VALUE>
-TCNN_DEVICE void accumulate_dy_dx(const Level<D>& lv, const Cell<D>& c, VALUE&& value, float (&grads)[F][D]) {
-#pragma unroll
-	for (uint32_t gd = 0; gd < D; ++gd) {
-#pragma unroll
-		for (uint32_t idx = 0; idx < (1u << (D - 1)); ++idx) {
-			float weight = lv.scale;
-			uint32_t corner = 0;  // corner with the gradient dimension at its low side
-#pragma unroll
-			for (uint32_t ngd = 0; ngd < D - 1; ++ngd) {
-				const uint32_t dim = ngd >= gd ? (ngd + 1) : ngd;
-				const uint32_t bit = (idx >> ngd) & 1u;
-				weight *= bit ? c.w[dim][1] : c.w[dim][0];
-				corner |= bit << dim;
-			}
-#pragma unroll
-			for (uint32_t f = 0; f < F; ++f) {
-				const float diff = value(corner | (1u << gd), f) - value(corner, f);
-				float t = weight * diff;
-				t = t * c.derivative[gd];
-				grads[f][gd] = grads[f][gd] + t;
-			}
-		}
-	}
-}
-
 template <uint32_t D, uint32_t F, bool DYDX, bool FAST>
 TCNN_DEVICE void grid_forward_sample(const Level<D>& lv, const GridIO& io, const half_t* __restrict__ grid, uint32_t level, uint32_t i,
                                      bool level_off, half_t* __restrict__ out, float* __restrict__ dy_dx) {
@@ -119,33 +88,6 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_forward(const GridMeta me
 //     and cut into 8 runs of equal cost, one per XCD (block b runs on XCD b % 8 -- observed, only speed depends on
 //     it): every XCD sees its 1-3 tables, 2 MiB each at the headline size, hot in its private 4 MiB L2.
 // ---------------------------------------------------------------------------------------------
-constexpr uint32_t FWD_MAX_SEGMENTS = 20;  // per XCD: ceil(MAX_N_LEVELS / 8) + the two cut levels at the ends of a run
-struct ForwardPlan {
-	uint32_t tiles;  // sample tiles per level
-	uint32_t n_segments[8];
-	// a run of one level's tiles with what the workgroup needs of that level (make_level's inputs): the workgroup's whole "what am I?" is ONE
-	// round of scalar loads -- the XCD's first four segments at once, searched in registers -- instead of a loop of dependent loads over the
-	// segments followed by a round for the level's table geometry (a workgroup lives a few microseconds: every round trip ahead of its first
-	// gather is occupancy the L2's line rate does not get)
-	struct Segment {
-		uint32_t level, tile_begin, tile_end, hashmap_size, resolution, scale_bits, offset, fast;
-	} segments[8][FWD_MAX_SEGMENTS];
-};
-constexpr uint32_t FWD_SEGMENTS_AT_ONCE = 4;
-template <uint32_t D>
-TCNN_DEVICE Level<D> level_of_segment(const GridMeta& meta, const ForwardPlan::Segment& seg) {
-	Level<D> lv;
-	lv.hashmap_size = seg.hashmap_size;
-	lv.resolution = seg.resolution;
-	lv.mask = seg.hashmap_size - 1u;
-	lv.scale = __builtin_bit_cast(float, seg.scale_bits);
-	lv.is_hash = meta.grid_type == (uint32_t)GridType::Hash;
-	lv.smooth = meta.interp == (uint32_t)InterpolationType::Smoothstep;
-	lv.nearest = meta.interp == (uint32_t)InterpolationType::Nearest;
-	lv.fast = (seg.fast & 1u) != 0u;  // (the plan stores 0 or 1)
-	return lv;
-}
-
 template <uint32_t D, uint32_t F, uint32_t SPT, bool FAST>
 TCNN_DEVICE void grid_forward_tile(const Level<D>& lv, const GridIO& io, const half_t* __restrict__ grid, uint32_t level, uint32_t first,
                                    const float (&x)[SPT][D], half_t* __restrict__ out) {
@@ -182,7 +124,8 @@ template <uint32_t D, uint32_t F, uint32_t SPT>
 __global__ void __launch_bounds__(GRID_THREADS) k_grid_forward_tiles(const GridMeta meta, const GridIO io, const ForwardPlan plan,
                                                                       const half_t* __restrict__ params, half_t* __restrict__ out) {
 	constexpr uint32_t TILE = GRID_THREADS * SPT;
-	// block -> (segment of its XCD's run, tile): level-major, so an XCD walks one table at a time
+	// block -> (segment of its XCD's run, tile): level-major, so an XCD walks one table at a time.  (forward_plan_item is this search as a
+	// function, for the fp32 gather; called from here it changed this kernel's instruction schedule, so the text stays.)
 	const uint32_t xcd = blockIdx.x & 7u;
 	uint32_t slot = blockIdx.x >> 3, tile = 0;
 	bool found = false;
@@ -262,8 +205,10 @@ __global__ void __launch_bounds__(GRID_THREADS) k_grid_forward_tiles(const GridM
 // tcnn.Encoding(dtype=torch.float32)).  Parameters, encoded features and gradients are fp32; the interpolation is the reference's
 // kernel_grid<float> -- fp32 weights, result = fma(weight, value, result) in fp32 (grid.h:144-163) --, the backward pass its
 // kernel_grid_backward<float, float>: one fp32 global atomic per corner and feature (grid.h:252-255; gradients of any magnitude survive,
-// nothing is scaled).  Not a hot path of the step (the trainer's encoding is 16-bit): one thread per (sample, level), the reference's
-// formulation; same index / weight code as the 16-bit kernels above.
+// nothing is scaled).  One thread per (sample, level), the reference's formulation; same index / weight code as the 16-bit kernels above.
+// The forward of every eikonal step (with dy_dx) and of every fp32 inference runs the tiled gather of grid_forward_f32.hip instead
+// (k_grid_forward_f32_tiles, the same arithmetic and bits); this kernel keeps the forms that one does not take -- a per-sample max_level,
+// Nearest, a null `out`, parameters off a 16-byte boundary, tcnn_set_fp32_grid_forward(0) -- and is what the host emulator runs.
 // =============================================================================================
 template <uint32_t D, uint32_t F, bool DYDX>
 __global__ void __launch_bounds__(GRID_THREADS) k_grid_forward_f32(const GridMeta meta, const GridIO io, const float* __restrict__ params, float* __restrict__ out,
@@ -337,82 +282,12 @@ __global__ void k_grid_indices(const GridMeta meta, const GridIO io, uint32_t* _
 	}
 }
 
-// Cuts the (level, tile) items, level-major, into 8 runs of equal cost.  Cost of an item (measured per kind of level,
-// profiles/r02_exp_forward.txt): 4 for a level whose table fits a CU's 32 KiB L1 next to the streaming traffic
-// (<= 24 KiB), 8 for a hashed level (one L2 line per corner pair), 11 for a larger densely indexed level, each times
-// (1 + 1.5 x the share of fetches that miss the L2) for tables beyond the L2 (T = 2^22: 16 MiB per level, 2.4x the
-// time of a 2 MiB level).  Falls back to uniform costs if a run would need more than FWD_MAX_SEGMENTS segments.
-static ForwardPlan make_forward_plan(const GridMeta& meta, uint32_t n, uint32_t tile_samples) {
-	for (int uniform = 0; uniform < 2; ++uniform) {
-		ForwardPlan plan = {};
-		plan.tiles = div_round_up(n, tile_samples);
-		uint64_t total = 0;
-		uint32_t cost[MAX_N_LEVELS];
-		for (uint32_t l = 0; l < meta.n_levels; ++l) {
-			const size_t table_bytes = (size_t)level_geometry(meta, l).entries * meta.n_feat * sizeof(half_t);
-			// What a (level, 512-sample tile) item costs, from per-workgroup clock stamps of this kernel on the headline and the T = 2^22 stress shape
-			// (scripts/exp_forward_stamps.*, profiles/r04_exp_notes.txt sections 18 and 20; microseconds of workgroup life, halved):
-			//   tables that fit the L1 (<= 24 KiB)                                   4
-			//   hashed levels: no locality at all                                    8 while the table fits the L2, x (1 + 2.5 miss) beyond it (16 MiB: 24)
-			//   dense levels: grid_index's stride arithmetic, but the corners of a   4.6 + 1.15 log2(table bytes / 24 KiB), the table capped at the L2's
-			//   cell are neighbours in y and z too                                   3 MiB, x (1 + 0.8 miss) beyond it  (55 KiB: 6, 1 MiB: 11, 7 MiB: 21)
-			// miss = share of the line fetches that miss the XCD's 4 MiB L2 (about 3 MiB of it hold the table while outputs stream through).
-			// Round 2's weights (dense 11 whatever the size, told from hashed by "no power-of-two size"; miss x 1.5 for both kinds) had the XCDs that
-			// hold the dense levels finish 8 us late on the headline (its dense levels ARE powers of two) and 40-87 us EARLY on the stress shape.
-			const bool hashed = level_geometry(meta, l).hashed;
-			const double miss = std::max(0.0, 1.0 - 3.0 * 1048576.0 / (double)table_bytes);
-			const double in_l2 = std::min((double)table_bytes, 3.0 * 1048576.0);
-			const double base = table_bytes <= 24u * 1024u ? 4.0
-			                    : hashed ? 8.0 * (1.0 + 2.5 * miss)
-			                             : (4.6 + 1.15 * std::log2(in_l2 / (24.0 * 1024.0))) * (1.0 + 0.8 * miss);
-			cost[l] = uniform ? 16u : (uint32_t)(4.0 * base + 0.5);  // (quarter-microsecond units: the cuts fall on whole tiles)
-			// A level the scalar max_level switches off gathers nothing: its items load positions and store zeros.  Weighed like the others they
-			// left the levels that are still on -- the coarse ones, all in the first XCDs' runs -- where they were, and the forward pass took as
-			// long as with every level on (measured: 0.082 ms at max_level 1.0, 0.5 and 0.25 alike).  A quarter of the cheapest kind.
-			if (!uniform && level_is_off<true>(meta, l, meta.n_feat)) cost[l] = 4u;
-			total += (uint64_t)cost[l] * plan.tiles;
-		}
-		bool ok = true;
-		uint64_t done = 0;  // cost of the items already assigned
-		uint32_t xcd = 0;
-		for (uint32_t l = 0; l < meta.n_levels && ok; ++l) {
-			const LevelGeometry geo = level_geometry(meta, l);
-			uint32_t t = 0;
-			while (t < plan.tiles) {
-				// XCD `xcd` takes items while the cost assigned so far stays below its cumulative share
-				const uint64_t limit = (total * (xcd + 1) + 7) / 8;
-				uint32_t take = (uint32_t)std::min<uint64_t>(plan.tiles - t, (limit - done + cost[l] - 1) / cost[l]);
-				if (xcd == 7) take = plan.tiles - t;
-				if (take > 0) {
-					uint32_t& ns = plan.n_segments[xcd];
-					if (ns == FWD_MAX_SEGMENTS) {
-						ok = false;
-						break;
-					}
-					plan.segments[xcd][ns++] = {l, t, t + take, geo.entries, meta.resolution[l], __builtin_bit_cast(uint32_t, meta.scale[l]), meta.offset[l], geo.fast ? 1u : 0u};
-					t += take;
-					done += (uint64_t)take * cost[l];
-				}
-				if (done >= limit && xcd < 7) ++xcd;
-			}
-		}
-		if (ok) return plan;
-	}
-	throw std::runtime_error("grid_forward: could not build the work plan");
-}
-
 template <uint32_t D, uint32_t F, uint32_t SPT>
 static void launch_forward_tiles(hipStream_t stream, const GridMeta& meta, const GridIO& io, const half_t* params, half_t* out) {
 	// (Gathering the levels whose table fits a CU's LDS out of LDS -- one launch per level, the table copied in by every workgroup -- was
 	// built in round 3 and measured slower in every arrangement: scripts/exp_grid_forward_lds.patch, profiles/r03_exp_notes.txt.)
 	const ForwardPlan plan = make_forward_plan(meta, io.n, GRID_THREADS * SPT);
-	uint32_t slots = 0;
-	for (uint32_t x = 0; x < 8; ++x) {
-		uint32_t n = 0;
-		for (uint32_t k = 0; k < plan.n_segments[x]; ++k) n += plan.segments[x][k].tile_end - plan.segments[x][k].tile_begin;
-		slots = std::max(slots, n);
-	}
-	TCNN_LAUNCH((k_grid_forward_tiles<D, F, SPT>), dim3(8u * slots), dim3(GRID_THREADS), 0, stream, meta, io, plan, params, out);
+	TCNN_LAUNCH((k_grid_forward_tiles<D, F, SPT>), dim3(forward_plan_blocks(plan)), dim3(GRID_THREADS), 0, stream, meta, io, plan, params, out);
 }
 
 void grid_forward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const half_t* params, half_t* out, float* dy_dx) {
@@ -437,6 +312,13 @@ void grid_forward(hipStream_t stream, const GridMeta& meta, const GridIO& io, co
 // ---- fp32 encodings (GridEncodingTemplated<float>) ----
 void grid_forward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* params, float* out, float* dy_dx) {
 	if (io.n == 0) return;
+#if !defined(TCNN_HOST_EMU)  // (the host emulator does not build the tiled fp32 gather: it runs the kernel below at every form)
+	// the tiled gather (grid_forward_f32.hip) takes the common forms; it loads a corner's features as 16-byte accesses, hence the alignment
+	if (out && ((uintptr_t)params & 15u) == 0u && grid_forward_f32_is_tiled(meta, io.max_level != nullptr)) {
+		launch_forward_f32_tiles(stream, meta, io, params, out, dy_dx);
+		return;
+	}
+#endif
 	const uint32_t blocks = grid_n_blocks(meta.n_levels, io.n);
 	grid_dispatch(meta, [&](auto D, auto F) {
 		if (dy_dx) {

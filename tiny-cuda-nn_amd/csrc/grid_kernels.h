@@ -114,7 +114,11 @@ void grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_feature
 //   * the reference's (k_grid_backward_atomic_f32: a memset of the levels it runs under Overwrite, one fp32 global atomic per corner and
 //     feature) for the other levels, for stochastic interpolation, for the second-order scatter (io.ddx set: its records follow another
 //     magnitude law) and for a caller without a workspace.
+// The forward has two kernels as well: the level-major tiled gather (grid_forward_f32.hip, with or without dy_dx; tcnn_set_fp32_grid_forward,
+// default on) and the reference's one thread per (sample, level), which keeps a per-sample max_level, Nearest, a null `out` and parameters
+// off a 16-byte boundary.  Same bits.  grid_forward_f32_is_tiled: what a call with an aligned table and an `out` takes now.
 void grid_forward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* params, float* out, float* dy_dx = nullptr);
+bool grid_forward_f32_is_tiled(const GridMeta& meta, bool per_sample_max_level);
 size_t grid_backward_f32_workspace_bytes(const GridMeta& meta, uint32_t n);  // 0: no level of this grid goes through the owner pass
 uint32_t grid_backward_f32_owner_levels(const GridMeta& meta, uint32_t n);   // levels that would (host arithmetic on the plan)
 void grid_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, float* grid_gradient, bool accumulate,

@@ -38,5 +38,8 @@ extern std::atomic<int> g_fp32_fused_second_order;
 // parameter gradients of an fp32 grid encoding: 1 = the owner pass on the levels its plan takes (grid_backward_f32.hip, default), 0 = the
 // reference's atomic kernel at every shape (tcnn_set_fp32_grid_backward; A/B runs, tests, the earlier bits)
 extern std::atomic<int> g_fp32_grid_backward;
+// forward of an fp32 grid encoding, with or without dy_dx: 1 = the level-major tiled gather on the forms it takes (grid_forward_f32.hip,
+// default), 0 = the reference's one thread per (sample, level) at every form (tcnn_set_fp32_grid_forward; A/B runs, tests).  Same bits.
+extern std::atomic<int> g_fp32_grid_forward;
 
 }  // namespace tcnn_hip

@@ -218,6 +218,9 @@ _sig("tcnn_module_fp32_fused_second_order", _i, _vp, _u32)
 _sig("tcnn_set_fp32_grid_backward", _i, _i)
 _sig("tcnn_get_fp32_grid_backward", _i)
 _sig("tcnn_module_fp32_grid_backward", _i, _vp, _u32)
+_sig("tcnn_set_fp32_grid_forward", _i, _i)
+_sig("tcnn_get_fp32_grid_forward", _i)
+_sig("tcnn_module_fp32_grid_forward", _i, _vp, _u32)
 _sig("tcnn_set_grid_owner_mode", _i, _i)
 _sig("tcnn_get_grid_owner_mode", _i)
 _sig("tcnn_grid_owner_wide_slices", _i, C.POINTER(C.c_uint64))
@@ -371,6 +374,16 @@ def set_fp32_grid_backward(enable):
     """Parameter gradients of fp32 grid encodings, process-wide: the owner pass (default: exact 64-bit sums on a per-level quantum, no
     floating-point global atomics, independent of the order of the samples) / the reference's atomic kernel at every shape."""
     _check(_lib.tcnn_set_fp32_grid_backward(int(bool(enable))))
+
+
+def get_fp32_grid_forward():
+    return bool(_lib.tcnn_get_fp32_grid_forward())
+
+
+def set_fp32_grid_forward(enable):
+    """Forward pass of fp32 grid encodings, with or without the input gradients' dy_dx, process-wide: the level-major tiled gather
+    (default) / one thread per (sample, level) at every form.  The same bits either way."""
+    _check(_lib.tcnn_set_fp32_grid_forward(int(bool(enable))))
 
 
 def get_grid_owner_mode():
@@ -536,6 +549,10 @@ class Module:
     def fp32_grid_backward(self, n):
         """1 if a backward call of n rows on this module would send at least one grid level through the fp32 owner pass now (set_fp32_grid_backward), else 0."""
         return int(_lib.tcnn_module_fp32_grid_backward(self._h, int(n)))
+
+    def fp32_grid_forward(self, n):
+        """1 if a forward call of n rows on this module would run the tiled fp32 gather on a grid of its encoding now (set_fp32_grid_forward), else 0."""
+        return int(_lib.tcnn_module_fp32_grid_forward(self._h, int(n)))
 
     def _takes_half(self, input):
         return input.dtype != torch.float32 and input.dtype == self._torch_param_dtype() and self.supports_half_input()
@@ -809,6 +826,7 @@ class ExtModule:
     fp32_fused_backward = Module.fp32_fused_backward
     fp32_fused_second_order = Module.fp32_fused_second_order
     fp32_grid_backward = Module.fp32_grid_backward
+    fp32_grid_forward = Module.fp32_grid_forward
 
 
 def ext_apply(module, x, params, loss_scale):
