@@ -511,8 +511,8 @@ int tcnn_module_fp32_fused_second_order(const tcnn_module_t* m, uint32_t n_eleme
  * Against the exact sum of the fp32 terms a value that `hits` terms reach is off by at most hits * q_v / 2 and one rounding to fp32;
  * Accumulate adds that sum to the stored value once per entry.  A level of zeros gives zeros;
  * NaN and Inf in dL_dy reach the entries they touch as NaN / Inf, as a floating-point sum would carry them.  0: the reference's formulation
- * at every shape (a memset and one fp32 global atomic per corner and feature), which is also what stochastic interpolation, levels outside
- * the plan and the second-order scatter run at either setting.  tcnn_module_fp32_grid_backward: 1 if a backward call of n_elements on this
+ * at every shape (a memset and one fp32 global atomic per corner and feature), which is also what stochastic interpolation and levels outside
+ * the plan run at either setting (the second-order scatter: tcnn_set_fp32_grid_second_order below).  tcnn_module_fp32_grid_backward: 1 if a backward call of n_elements on this
  * module would send at least one grid level through the owner pass now; 0 for 16-bit modules, modules without a grid, stochastic grids
  * and with the switch off. */
 int tcnn_set_fp32_grid_backward(int enable);
@@ -528,6 +528,22 @@ int tcnn_module_fp32_grid_backward(const tcnn_module_t* m, uint32_t n_elements);
 int tcnn_set_fp32_grid_forward(int enable);
 int tcnn_get_fp32_grid_forward(void);
 int tcnn_module_fp32_grid_forward(const tcnn_module_t* m, uint32_t n_elements);
+/* Second-order pass (tcnn_module_backward_backward_input) of a lone fp32 grid encoding, process-wide, a mask of two bits, default 1
+ * (csrc/grid_second_order_f32.hip): bit 0 on; bit 1 off, because it measured faster at the headline grid and slower at a grid of small tables.
+ *   bit 0: dL_dparams through the owner pass of tcnn_set_fp32_grid_backward -- the second-order records binned by the owning table slice and
+ *          summed in 64-bit integers on the same quantum per value (taken from the largest term that reaches it, so the rule holds for this
+ *          scatter's weights as well): no floating-point atomics, no memset of the table, the same bits for any order of the samples and in
+ *          every run.  Also needs tcnn_set_fp32_grid_backward(1); not for Nearest (no second derivative: zeros) or stochastic interpolation.
+ *   bit 1: dL_dinput level-major and tiled -- a workgroup per (level, sample tile), eight runs of equal cost, one per XCD, the level's D sums
+ *          stored per level and added in ascending order by a second kernel: the same bits as the other route.  Not for Nearest, a
+ *          per-sample max_level array or parameters off a 16-byte boundary.
+ * A cleared bit: the reference's formulation (a memset of the table and one fp32 global atomic per corner and feature / one thread per
+ * sample walking the levels).  Values outside 0..3 are refused.  tcnn_module_fp32_grid_second_order: the bits a backward_backward_input call
+ * of n_elements on this module would take now; 0 for 16-bit modules, anything that is not a lone fp32 grid, with tcnn_set_fp32_second_order(1)
+ * and for n_elements == 0. */
+int tcnn_set_fp32_grid_second_order(int mask);
+int tcnn_get_fp32_grid_second_order(void);
+int tcnn_module_fp32_grid_second_order(const tcnn_module_t* m, uint32_t n_elements);
 /* Accumulator form of the bucket owners in mode 3, process-wide (same bits from all three): 0 = packed (default: both features of a
  * payload word in one 64-bit LDS word, half the LDS atomics and half the LDS; slices whose sums could leave int32 are redone wide),
  * 1 = 64-bit fixed point per value throughout, 2 = the packed kernel with every slice through its wide redo (tests). */

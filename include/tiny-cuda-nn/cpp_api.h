@@ -155,6 +155,9 @@ public:
 	bool fp32_fused_backward(uint32_t n_elements) const { return tcnn_module_fp32_fused_backward(m_, n_elements) != 0; }
 	// ... and would a backward_backward_input call run the fused fp32 second-order kernels now (tcnn_set_fp32_fused_second_order)
 	bool fp32_fused_second_order(uint32_t n_elements) const { return tcnn_module_fp32_fused_second_order(m_, n_elements) != 0; }
+	// ... and which bits of tcnn_set_fp32_grid_second_order a backward_backward_input call on a lone fp32 grid would take now (1: dL_dparams
+	// through the owner pass, 2: the tiled dL_dinput)
+	int fp32_grid_second_order(uint32_t n_elements) const { return tcnn_module_fp32_grid_second_order(m_, n_elements); }
 	void inference_half_input(hipStream_t stream, uint32_t n_elements, const void* input, void* output, void* params) {
 		check(tcnn_module_inference_half_input(m_, stream, n_elements, input, output, params));
 	}

@@ -245,6 +245,25 @@ int tcnn_module_fp32_grid_forward(const tcnn_module_t* m, uint32_t n_elements) {
 	}
 	return 0;
 }
+// The bits of tcnn_set_fp32_grid_second_order that the fp32 kernels of a backward_backward_input call of n_elements on a lone grid take:
+// bit 0, the parameter gradient through the owner pass (host arithmetic on the plan; no level of a Nearest or stochastic grid, and not
+// without tcnn_set_fp32_grid_backward), bit 1, the tiled input gradient (not Nearest, not with a per-sample max_level).
+static int fp32_grid_second_order_route(const EncodingDesc& e, const GridMeta& grid, uint32_t n_elements, bool per_sample_max_level) {
+	const int mask = g_fp32_grid_second_order.load();
+	int bits = 0;
+	if ((mask & 1) && g_fp32_grid_backward.load() != 0 && e.n_params > 0 && grid.interp != (uint32_t)InterpolationType::Nearest &&
+	    grid_backward_f32_owner_levels(grid, n_elements) > 0) {
+		bits |= 1;
+	}
+	if ((mask & 2) && grid_backward_backward_input_f32_is_tiled(grid, per_sample_max_level)) bits |= 2;
+	return bits;
+}
+// what tcnn_module_backward_backward_input decides for a call of n_elements on this module now: 0 unless it is a lone fp32 grid on the fp32
+// kernels (tcnn_set_fp32_second_order(0))
+int tcnn_module_fp32_grid_second_order(const tcnn_module_t* m, uint32_t n_elements) {
+	if (!m || !m->fp32_io || n_elements == 0 || g_fp32_second_order.load() != 0 || m->md.has_network || !m->md.enc.is_grid()) return 0;
+	return fp32_grid_second_order_route(m->md.enc, m->md.enc.grid, n_elements, m->md.enc.max_level_gpu != nullptr);
+}
 // what mlp_f32_backward_backward decides for a backward_backward_input call of n_elements on this module
 int tcnn_module_fp32_fused_second_order(const tcnn_module_t* m, uint32_t n_elements) {
 	return m && m->fp32_network() && mlp_f32_backward_backward_is_fused(m->md.net.mlp, n_elements) ? 1 : 0;
@@ -354,10 +373,25 @@ int tcnn_module_backward_backward_input(tcnn_module_t* m, tcnn_stream_t stream_,
 			                                 (float*)dL_ddLdoutput);
 		}
 		if ((dL_dparams || dL_dinput) && !dL_doutput) throw std::runtime_error("backward_backward_input: dL_doutput is required for parameter / input gradients");
-		if (dL_dparams && e.n_params > 0) grid_backward(stream, grid, io, (const float*)dL_doutput, (float*)dL_dparams, false);  // grid.h:942-975, GradientMode::Overwrite
+		const int route = fp32_grid_second_order_route(e, grid, n, io.max_level != nullptr);
+		if (dL_dparams && e.n_params > 0) {  // grid.h:942-975, GradientMode::Overwrite
+			GridBackwardWorkspace ws;  // the owner pass's workspace, stream-ordered: the records of the first-order pass, so its size
+			Scratch queues;
+			if (route & 1) {
+				queues = Scratch(stream, grid_backward_f32_workspace_bytes(grid, n));
+				ws.scratch = queues.ptr;
+				ws.scratch_bytes = queues.bytes;
+			}
+			grid_backward(stream, grid, io, (const float*)dL_doutput, (float*)dL_dparams, false, ws);
+		}
 		if (dL_dinput) {  // grid.h:977-1010
 			if (!params) throw std::runtime_error("backward_backward_input: params are required for the input gradient");
-			grid_backward_backward_input(stream, grid, io, (const float*)dL_doutput, (const float*)params, dL_dinput, md.n_input_dims, 1u);
+			if ((route & 2) && ((uintptr_t)params & 15u) == 0) {
+				Scratch partial(stream, std::max<size_t>(grid_backward_backward_input_f32_partial_bytes(grid, n), sizeof(float)));
+				grid_backward_backward_input_f32_tiled(stream, grid, io, (const float*)dL_doutput, (const float*)params, dL_dinput, md.n_input_dims, 1u, partial.as<float>());
+			} else {
+				grid_backward_backward_input(stream, grid, io, (const float*)dL_doutput, (const float*)params, dL_dinput, md.n_input_dims, 1u);
+			}
 		}
 		return TCNN_OK;
 	}

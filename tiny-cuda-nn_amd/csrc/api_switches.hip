@@ -46,6 +46,7 @@ std::atomic<int> g_fp32_fused_backward{1};
 std::atomic<int> g_fp32_fused_second_order{1};
 std::atomic<int> g_fp32_grid_backward{1};
 std::atomic<int> g_fp32_grid_forward{1};
+std::atomic<int> g_fp32_grid_second_order{1};  // bit 1 (the tiled input gradient) is not faster at both measured grids: DESIGN.md section 8
 
 }  // namespace tcnn_hip
 
@@ -184,6 +185,12 @@ int tcnn_set_fp32_grid_backward(int enable) {
 int tcnn_get_fp32_grid_forward(void) { return g_fp32_grid_forward.load(); }
 int tcnn_set_fp32_grid_forward(int enable) {
 	g_fp32_grid_forward.store(enable != 0 ? 1 : 0);
+	return TCNN_OK;
+}
+int tcnn_get_fp32_grid_second_order(void) { return g_fp32_grid_second_order.load(); }
+int tcnn_set_fp32_grid_second_order(int mask) {
+	if (mask < 0 || mask > 3) return TCNN_ERROR;
+	g_fp32_grid_second_order.store(mask);
 	return TCNN_OK;
 }
 int tcnn_get_fp32_fused_second_order(void) { return g_fp32_fused_second_order.load(); }

@@ -456,9 +456,10 @@ void grid_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, c
                    const GridBackwardWorkspace& ws) {
 	if (io.n == 0) return;
 	if (!grid_gradient) throw std::runtime_error("grid_backward: missing gradient buffer");
-	// the owner pass takes the levels of its plan when the caller brought its workspace; the second-order scatter (io.ddx) stays on the atomics
+	// the owner pass takes the levels of its plan when the caller brought its workspace, for the second-order scatter (io.ddx) as for the first
+	// order; Nearest has no second derivative, so that scatter of it plans nothing and zeroes the table
 	F32BackwardPlan bp;
-	if (!io.ddx && ws.scratch) {
+	if (ws.scratch && !(io.ddx && meta.interp == (uint32_t)InterpolationType::Nearest)) {
 		bp = f32_backward_plan(meta, io.n);
 		if (ws.scratch_bytes < bp.workspace_bytes) throw std::runtime_error("grid_backward: workspace too small for the fp32 owner pass");
 	}

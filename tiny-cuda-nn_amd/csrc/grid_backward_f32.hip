@@ -8,7 +8,8 @@
 //   k_f32_scan     one workgroup: exclusive prefix of all slice counts -- slice s owns records [start[s], start[s] + count[s]) of the queue;
 //   k_f32_records  <scatter> the same tiles again: derives each corner ONCE more with its fp32 term, ranks it within its slice by an integer
 //                  LDS atomic, reserves the tile's part of every slice's run with one global integer atomic per non-empty slice, and writes
-//                  the records {entry within the slice, F terms} there;
+//                  the records {entry within the slice, F terms} there (the second-order scatter, io.ddx set: k_f32_second_order_records of
+//                  grid_second_order_f32.hip in this place -- the same entries, so the same counts and runs, with the second-order term);
 //   k_f32_owner    a workgroup per slice: streams its run twice -- first the largest |term| of every value (integer LDS maxima), which fixes
 //                  the value's quantum, then every term rounded once on that quantum into a 64-bit LDS sum (ds_add_u64: dense integer LDS
 //                  atomics cost 11 clk per wave instruction, floating-point ones ~170; the second pass finds the run in L2) -- converts each
@@ -225,7 +226,11 @@ void launch_f32_owner_backward(hipStream_t stream, const GridMeta& meta, const G
 	grid_dispatch(meta, [&](auto D, auto F) {
 		TCNN_LAUNCH((k_f32_records<D, F, true>), dim3(record_blocks), dim3(F32_SCATTER_THREADS), record_lds, stream, meta, io, plan, dL_dy, control, queues);
 		TCNN_LAUNCH(k_f32_scan, dim3(1), dim3(SLICED_THREADS), 0, stream, plan, control);
-		TCNN_LAUNCH((k_f32_records<D, F, false>), dim3(record_blocks), dim3(F32_SCATTER_THREADS), record_lds, stream, meta, io, plan, dL_dy, control, queues);
+		if (io.ddx) {  // the second-order records: the same runs, another term (grid_second_order_f32.hip)
+			launch_f32_second_order_scatter(stream, meta, io, plan, dL_dy, control, queues, record_blocks, record_lds);
+		} else {
+			TCNN_LAUNCH((k_f32_records<D, F, false>), dim3(record_blocks), dim3(F32_SCATTER_THREADS), record_lds, stream, meta, io, plan, dL_dy, control, queues);
+		}
 		TCNN_SET_MAX_DYN_LDS((k_f32_owner<F>), F32_OWNER_LDS_BYTES);
 		TCNN_LAUNCH((k_f32_owner<F>), dim3(plan.n_slices_total), dim3(SLICED_THREADS), F32_OWNER_LDS_BYTES, stream, table, plan, (const uint32_t*)control, (const uint32_t*)queues,
 		            grid_gradient, accumulate ? 1 : 0);

@@ -313,6 +313,14 @@ inline BackwardPlan make_backward_plan(const GridMeta& meta, uint32_t n, bool pa
 // the maximum and sets a flag on its value instead of entering the sum; at the store a flagged value becomes what a floating-point sum in any
 // order would have given -- NaN if a NaN or both infinities were seen, else the infinity seen -- so the owners propagate what the atomic
 // kernel produces and the other values keep their exact sums.
+//
+// The second-order scatter (io.ddx set; grid_second_order_f32.hip) goes through the same plan with the same counts: a record's slice depends
+// on its entry index alone.  Its term is t = w2 * dL_dy with w2 = scale * sum_d ddx[d] * pos'(d) * (+-1) * prod_{e != d} w_e, which is not
+// bounded by one -- and the rule does not ask for that.  The owner takes 2^(e_v - 1) <= max |t| < 2^e_v from the terms themselves, so
+// |t / q_v| < 2^(62 - ceil(log2 n) - D) as before, a value still receives at most n * 2^D terms, and every sum stays inside int64.  The error
+// per value is at most hits * q_v / 2 plus the one conversion to fp32, with q_v <= 2^(ceil(log2 n) + D - 61) * max |t|: at 4352 samples and
+// D = 4 that is 2^-44 of the value's largest term, against the 2^-24 of one fp32 rounding.  Only the per-level bound q_l is lost (it rests
+// on weights of at most one); nothing uses it.  Nearest has no second derivative: the plan takes no level of it for this scatter.
 constexpr uint32_t F32_SCATTER_THREADS = 256;
 constexpr uint32_t F32_RECORDS_PER_LANE = 16;   // a lane of the counting / scatter launches holds 16 >> D samples: 16 records
 constexpr uint32_t F32_OWNER_VALUES = 8192;     // gradient values of a slice at the most: a 64-bit sum, a 32-bit maximum and 4 flag bits each
@@ -343,9 +351,9 @@ struct F32BackwardPlan {
 	size_t queue_offset = 0, workspace_bytes = 0;  // control block at offset 0 of the workspace, then the queues
 };
 
-// Which levels of an fp32 grid the owner pass takes for a first-order backward of n samples, and where its state lies.  Stochastic
-// interpolation (one unweighted update per sample and level) stays on the atomic kernel, as in the 16-bit plan; so does the second-order
-// scatter (the caller does not plan it: its records follow another magnitude law).
+// Which levels of an fp32 grid the owner pass takes for a backward of n samples, first order or second (the same records per level, so the
+// same plan and workspace; a Nearest grid's second-order scatter is not planned by its caller), and where its state lies.  Stochastic
+// interpolation (one unweighted update per sample and level) stays on the atomic kernel, as in the 16-bit plan.
 inline F32BackwardPlan make_f32_backward_plan(const GridMeta& meta, uint32_t n) {
 	F32BackwardPlan bp;
 	if (n == 0 || meta.stochastic != 0u) return bp;
@@ -390,6 +398,9 @@ inline F32BackwardPlan make_f32_backward_plan(const GridMeta& meta, uint32_t n) 
 // the launches of that pass over the taken levels (grid_backward_f32.hip): clear, count, scan, scatter, owners
 void launch_f32_owner_backward(hipStream_t stream, const GridMeta& meta, const GridIO& io, const F32BackwardPlan& bp, const float* dL_dy, void* workspace,
                                float* grid_gradient, bool accumulate);
+// the scatter launch of that sequence when io.ddx is set (grid_second_order_f32.hip): the geometry and LDS of the first-order scatter
+void launch_f32_second_order_scatter(hipStream_t stream, const GridMeta& meta, const GridIO& io, const F32OwnerPlan& plan, const float* dL_dy, uint32_t* control, uint32_t* queues,
+                                     uint32_t record_blocks, uint32_t record_lds);
 
 // The two passes of the bucketed mode, each launched from the file that holds its kernel (grid_backward_scatter.hip, grid_backward_owner.hip);
 // grid_backward.hip runs them in turn.  `counters`, `queues`, `overflow`: the three parts of the GridBackwardWorkspace.

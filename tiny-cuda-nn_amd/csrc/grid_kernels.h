@@ -112,8 +112,9 @@ void grid_backward_input(hipStream_t stream, uint32_t n_dims, uint32_t n_feature
 //     the sum to the stored value once per entry.  It takes every level of the first 32 that has at most 4096 slices, while the records of
 //     the taken levels stay below 2^32;
 //   * the reference's (k_grid_backward_atomic_f32: a memset of the levels it runs under Overwrite, one fp32 global atomic per corner and
-//     feature) for the other levels, for stochastic interpolation, for the second-order scatter (io.ddx set: its records follow another
-//     magnitude law) and for a caller without a workspace.
+//     feature) for the other levels, for stochastic interpolation and for a caller without a workspace.
+// The second-order scatter (io.ddx set) takes the same two routes by the same rule, with the same workspace size: the owner pass sums its
+// records as it sums the first-order ones (grid_second_order_f32.hip forms them; grid_backward_plan.h says why the quantum rule carries over).
 // The forward has two kernels as well: the level-major tiled gather (grid_forward_f32.hip, with or without dy_dx; tcnn_set_fp32_grid_forward,
 // default on) and the reference's one thread per (sample, level), which keeps a per-sample max_level, Nearest, a null `out` and parameters
 // off a 16-byte boundary.  Same bits.  grid_forward_f32_is_tiled: what a call with an aligned table and an `out` takes now.
@@ -139,11 +140,19 @@ void grid_backward_backward_dLdoutput(hipStream_t stream, uint32_t n_dims, uint3
 void grid_backward_backward_input(hipStream_t stream, const GridMeta& meta, const GridIO& io, const half_t* dL_dy, const half_t* params,
                                   float* dL_dx, uint32_t dx_stride_i, uint32_t dx_stride_d);
 // The same three for an fp32 encoding (the reference's T = float instances of these kernels): fp32 parameters, dL_dy and results, nothing
-// rounded through 16 bits.  The parameter part is the fp32 grid_backward() with io.ddx set (one fp32 global atomic per corner and feature).
+// rounded through 16 bits.  The parameter part is the fp32 grid_backward() with io.ddx set: the owner pass for a caller that brings its
+// workspace, one fp32 global atomic per corner and feature otherwise.
 void grid_backward_backward_dLdoutput(hipStream_t stream, uint32_t n_dims, uint32_t n_features, uint32_t n_to_pad, const GridIO& io, const float* dy_dx,
                                       float* dL_ddLdy);
 void grid_backward_backward_input(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, const float* params, float* dL_dx,
                                   uint32_t dx_stride_i, uint32_t dx_stride_d);
+// The input gradient level-major and tiled (grid_second_order_f32.hip; bit 1 of tcnn_set_fp32_grid_second_order): the same bits as the
+// kernel above.  is_tiled: what a call with parameters on a 16-byte boundary takes now -- not with a per-sample max_level, not Nearest.
+// `partial`: partial_bytes() of device memory the call may scribble on (one row per level that the scalar max_level leaves on).
+bool grid_backward_backward_input_f32_is_tiled(const GridMeta& meta, bool per_sample_max_level);
+size_t grid_backward_backward_input_f32_partial_bytes(const GridMeta& meta, uint32_t n);
+void grid_backward_backward_input_f32_tiled(hipStream_t stream, const GridMeta& meta, const GridIO& io, const float* dL_dy, const float* params, float* dL_dx, uint32_t dx_stride_i,
+                                            uint32_t dx_stride_d, float* partial);
 
 // Debug/parity helper: entry index per (sample, level, corner) -> indices[(i*L + l)*2^D + c]
 void grid_indices(hipStream_t stream, const GridMeta& meta, const GridIO& io, uint32_t* indices);

@@ -41,5 +41,10 @@ extern std::atomic<int> g_fp32_grid_backward;
 // forward of an fp32 grid encoding, with or without dy_dx: 1 = the level-major tiled gather on the forms it takes (grid_forward_f32.hip,
 // default), 0 = the reference's one thread per (sample, level) at every form (tcnn_set_fp32_grid_forward; A/B runs, tests).  Same bits.
 extern std::atomic<int> g_fp32_grid_forward;
+// second-order pass of a lone fp32 grid encoding, a mask (tcnn_set_fp32_grid_second_order; grid_second_order_f32.hip): bit 0 = the parameter
+// gradient through the owner pass (also needs g_fp32_grid_backward; default on), bit 1 = the level-major tiled input gradient (default off:
+// slower where every table is L2-resident).  A cleared bit: the atomic
+// scatter behind a memset of the table / one thread per sample walking the levels (A/B runs, tests, the earlier bits of dL_dparams).
+extern std::atomic<int> g_fp32_grid_second_order;
 
 }  // namespace tcnn_hip

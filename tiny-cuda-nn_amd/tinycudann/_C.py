@@ -221,6 +221,9 @@ _sig("tcnn_module_fp32_grid_backward", _i, _vp, _u32)
 _sig("tcnn_set_fp32_grid_forward", _i, _i)
 _sig("tcnn_get_fp32_grid_forward", _i)
 _sig("tcnn_module_fp32_grid_forward", _i, _vp, _u32)
+_sig("tcnn_set_fp32_grid_second_order", _i, _i)
+_sig("tcnn_get_fp32_grid_second_order", _i)
+_sig("tcnn_module_fp32_grid_second_order", _i, _vp, _u32)
 _sig("tcnn_set_grid_owner_mode", _i, _i)
 _sig("tcnn_get_grid_owner_mode", _i)
 _sig("tcnn_grid_owner_wide_slices", _i, C.POINTER(C.c_uint64))
@@ -384,6 +387,17 @@ def set_fp32_grid_forward(enable):
     """Forward pass of fp32 grid encodings, with or without the input gradients' dy_dx, process-wide: the level-major tiled gather
     (default) / one thread per (sample, level) at every form.  The same bits either way."""
     _check(_lib.tcnn_set_fp32_grid_forward(int(bool(enable))))
+
+
+def get_fp32_grid_second_order():
+    return int(_lib.tcnn_get_fp32_grid_second_order())
+
+
+def set_fp32_grid_second_order(mask):
+    """Second-order pass of a lone fp32 grid encoding, process-wide, a mask (default 1): bit 0 = dL_dparams through the owner pass (exact
+    integer sums, no memset of the table, the same bits in any order and every run), bit 1 = dL_dinput level-major and tiled (the same bits);
+    a cleared bit = the atomic scatter / one thread per sample.  Values outside 0..3 are refused."""
+    _check(_lib.tcnn_set_fp32_grid_second_order(int(mask)))
 
 
 def get_grid_owner_mode():
@@ -553,6 +567,10 @@ class Module:
     def fp32_grid_forward(self, n):
         """1 if a forward call of n rows on this module would run the tiled fp32 gather on a grid of its encoding now (set_fp32_grid_forward), else 0."""
         return int(_lib.tcnn_module_fp32_grid_forward(self._h, int(n)))
+
+    def fp32_grid_second_order(self, n):
+        """The bits of set_fp32_grid_second_order a bwd_bwd_input call of n rows on this module would take now; 0 unless it is a lone fp32 grid."""
+        return int(_lib.tcnn_module_fp32_grid_second_order(self._h, int(n)))
 
     def _takes_half(self, input):
         return input.dtype != torch.float32 and input.dtype == self._torch_param_dtype() and self.supports_half_input()
@@ -827,6 +845,7 @@ class ExtModule:
     fp32_fused_second_order = Module.fp32_fused_second_order
     fp32_grid_backward = Module.fp32_grid_backward
     fp32_grid_forward = Module.fp32_grid_forward
+    fp32_grid_second_order = Module.fp32_grid_second_order
 
 
 def ext_apply(module, x, params, loss_scale):
